@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- alt_bn128 G1 Pippenger MSM throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--total-log2n T]
+    python bench.py --gpus N --steps K --warmup W [--total-log2n T] [--dump-outputs DIR] [--full]
 
 One "step" = one multi-scalar multiplication through the C-ABI with bases (prepared affine,
 64 B) and scalars (Montgomery Fr, 32 B) already resident in HBM.
@@ -18,18 +18,26 @@ One "step" = one multi-scalar multiplication through the C-ABI with bases (prepa
 
 Inputs follow SURVEY.md section 8(d): scalars uniform in [0, r) from splitmix64-seeded
 xoshiro256** (seed 0x4C45474F534E4152); bases P_i = (a + i*b)*G1, handed to the library as
-un-normalised Jacobian points (random Z) and, in a second run, normalised (Z = 1).  The result
-of the timed loop's last step is checked by the known-discrete-log identity.
+un-normalised Jacobian points (random Z) and, in a second run (--full), normalised (Z = 1).  The
+result of the timed loop's last step is checked by the known-discrete-log identity.
 
-Prints ONE JSON line (rank 0) with the throughput, a `roofline` object for the dominant kernel
-(bucket accumulation; 96 algorithmic bytes per pair against the HBM peak, plus the field-
-multiplication rate against the measured integer ceiling, which is what really bounds it), a
-`cpu_baseline` object (the oracle = libff-algorithm restatement, timed on this host) and a `configs`
-block: the other BASELINE.json configs (G2 MSM 2^20, CPpoly d=20, the 2^12-pairing product, the CPhad
-verifier shape, the CPlink prover MSM), each result-checked, each with its time, algorithmic bytes and
-field-multiplication rate (legosnark_amd/benchcfg.py).  `unchanged_reference_binary`: the reference's own
-`hadamard 20` example (unchanged source, built against the shim; a child process) with ITS timers
-(`##had_sc ... Prove/Verify`, src/examples/hadamard.cc:98-105) and the time it spent inside the library.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+throughput, `ms_per_step` and a `roofline` object for the dominant kernel (bucket accumulation; 96
+algorithmic bytes per pair against the HBM peak, plus the field-multiplication rate against the
+measured integer ceiling, which is what really bounds it), both from the timed steps themselves.
+`--dump-outputs DIR` writes the last timed step's result to DIR/msm_g1_affine_xy.npy: the affine
+point (x, y) as canonical integers mod p, eight little-endian 32-bit limbs each, float64 (exact).
+
+`--full` adds everything that takes runs of its own: the PMC child runs behind `roofline.traffic`,
+the single-call latency, the normalised-bases run, the CPlink prover (resident and host path, with
+cold runs in fresh processes), the 2^24+2 sharded run when N > 1, a `cpu_baseline` object (the
+oracle = libff-algorithm restatement, timed on this host) and a `configs` block: the other
+BASELINE.json configs (G2 MSM 2^20, CPpoly d=20, the 2^12-pairing product, the CPhad verifier
+shape, the CPlink prover MSM), each result-checked, each with its time, algorithmic bytes and
+field-multiplication rate (legosnark_amd/benchcfg.py).  `unchanged_reference_binary`: the
+reference's own `hadamard 20` example (unchanged source, built against the shim into oracle/_ref/;
+a child process) with ITS timers (`##had_sc ... Prove/Verify`, src/examples/hadamard.cc:98-105)
+and the time it spent inside the library.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks (one child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, started before this process
@@ -50,6 +58,7 @@ ALG_BYTES_PER_PAIR = 96        # 64 B affine point + 32 B scalar
 # rate of the dominant kernel against the measured chip-wide ceiling of the 29-bit-limb
 # Montgomery product (tools/ubench_int.hip: 175 G mults/s at >= 4 waves/SIMD).
 FMUL_PEAK_G = 175.0
+REF_BIN = os.path.join("oracle", "_ref")   # the reference's own programs, built by oracle/reference.mk
 
 
 def cpu_model():
@@ -110,22 +119,25 @@ def pmc_traffic(kernel_substr="k_accumulate", exclude="heavy", timeout_s=150, ex
 
 
 def reference_binary_run(d=20):
-    """The reference's UNCHANGED `hadamard` example (built against the shim by __graft_entry__.build() where
-    /root/reference exists; build/ travels with the snapshot) run as a child process at d variables, with the
+    """The reference's UNCHANGED `hadamard` example (built against the shim into oracle/_ref/ by __graft_entry__.build()
+    where the reference's sources exist; oracle/_ref/ travels with the tree) run as a child process at d variables, with the
     reference's own timers (##had_sc ... Prove/Verify: N micros, src/examples/hadamard.cc:98-105) and the shim's
     accounting of the time spent inside the library (LSA_SHIM_STATS=1).  What a LegoSNARK user sees end to end."""
     import re
     import subprocess
     # the binary the reference's OWN CMakeLists.txt builds (its flags: OPT_FLAGS "-O3 -ggdb", -Wall -Wextra -Wfatal-errors,
     # /root/reference/CMakeLists.txt:27-33,54-64) against the drop-in packages; the Makefile build (-O3 -w) if that is absent
-    rel = os.path.join("build", "reference_cmake", "src", "examples", "hadamard")
+    rel = os.path.join(REF_BIN, "reference_cmake", "src", "examples", "hadamard")
     how = "the reference's CMakeLists.txt, default configuration (-O3 -ggdb, MULTICORE=OFF)"
     if not os.path.exists(os.path.join(ROOT, rel)):
-        rel, how = os.path.join("build", "reference", "hadamard"), "legosnark_amd/shim/Makefile (-O3)"
+        rel, how = os.path.join(REF_BIN, "reference", "hadamard"), "legosnark_amd/shim/Makefile (-O3)"
     exe = os.path.join(ROOT, rel)
     if not os.path.exists(exe):
         return {"program": rel, "status": "absent (built only where the reference's sources are)"}
-    env = dict(os.environ, LSA_SHIM_STATS="1")
+    # the binaries' run path names the directory they were linked in: they load this tree's library
+    lib_path = os.path.join(ROOT, "legosnark_amd") + (":" + os.environ["LD_LIBRARY_PATH"] if os.environ.get("LD_LIBRARY_PATH") else "")
+    base_env = dict(os.environ, LD_LIBRARY_PATH=lib_path)
+    env = dict(base_env, LSA_SHIM_STATS="1")
     t0 = time.perf_counter()
     try:
         r = subprocess.run([exe, str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
@@ -137,13 +149,13 @@ def reference_binary_run(d=20):
     for m in re.finditer(r"^##(\S+) (.*?): ([0-9.e+]+) micros", r.stdout, re.M):
         res["timers_ms"]["%s %s" % (m.group(1), m.group(2))] = round(float(m.group(3)) / 1e3, 3)
     # the reference's -DMULTICORE=ON configuration (-fopenmp -DMULTICORE=1: chunks = threads, lipmaa.cc's OpenMP loops)
-    mc = os.path.join(ROOT, "build", "reference_cmake_mc", "src", "examples", "hadamard")
+    mc = os.path.join(ROOT, REF_BIN, "reference_cmake_mc", "src", "examples", "hadamard")
     if os.path.exists(mc):
         try:
             nthr = str(min(8, len(os.sched_getaffinity(0))))
-            m_ = subprocess.run([mc, str(d)], env=dict(os.environ, OMP_NUM_THREADS=nthr), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+            m_ = subprocess.run([mc, str(d)], env=dict(base_env, OMP_NUM_THREADS=nthr), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
             tm = {"%s %s" % (x.group(1), x.group(2)): round(float(x.group(3)) / 1e3, 3) for x in re.finditer(r"^##(\S+) (.*?): ([0-9.e+]+) micros", m_.stdout, re.M)}
-            res["multicore_build"] = {"program": "build/reference_cmake_mc/src/examples/hadamard %d (-DMULTICORE=ON)" % d, "rc": m_.returncode, "omp_threads": int(nthr),
+            res["multicore_build"] = {"program": "%s/reference_cmake_mc/src/examples/hadamard %d (-DMULTICORE=ON)" % (REF_BIN, d), "rc": m_.returncode, "omp_threads": int(nthr),
                                       "nchunks_printed": sorted(set(re.findall(r"NCHUNKS : (\d+)", m_.stdout))),
                                       "timers_ms": {k: v for k, v in tm.items() if "TOTAL" in k or "lipmaa" in k}}
         except Exception as e:
@@ -151,22 +163,22 @@ def reference_binary_run(d=20):
     # rc 0 says little (the reference's verifiers print nothing when a check fails): the verifier side of
     # the same build is checked beside it -- legosnark_amd/shim/checks/pairing_check.cc runs the reference's own
     # simple_pairing_check on true and false statements and its unchanged CPPoly::verify, deferred and call by call
-    chk = os.path.join(ROOT, "build", "reference", "pairing_check")
+    chk = os.path.join(ROOT, REF_BIN, "reference", "pairing_check")
     if os.path.exists(chk):
         try:
-            c = subprocess.run([chk, "12"], env=dict(os.environ, LSA_SEED="11"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+            c = subprocess.run([chk, "12"], env=dict(base_env, LSA_SEED="11"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
             last = json.loads(c.stdout.strip().splitlines()[-1]) if c.stdout.strip() else {}
-            res["verifier_check"] = {"program": "build/reference/pairing_check 12", "rc": c.returncode, "failures": last.get("failures"),
+            res["verifier_check"] = {"program": "%s/reference/pairing_check 12" % REF_BIN, "rc": c.returncode, "failures": last.get("failures"),
                                      "cppoly_verify": last.get("cppoly_verify"), "cppoly_verify_ms": last.get("cppoly_verify_ms")}
         except Exception as e:                               # a broken check is reported, not hidden
-            res["verifier_check"] = {"program": "build/reference/pairing_check 12", "error": str(e)[:200]}
+            res["verifier_check"] = {"program": "%s/reference/pairing_check 12" % REF_BIN, "error": str(e)[:200]}
     # the same prover with its vectors resident on the device (legosnark_amd/shim/checks/resident_prover_check.cc): CPHad's
     # prove written against the C-ABI, fed the inputs and the random stream of the unchanged CPHad::prove, every proof
     # element compared, the resident proof accepted by the reference's verifier
-    rp = os.path.join(ROOT, "build", "reference", "resident_prover_check")
+    rp = os.path.join(ROOT, REF_BIN, "reference", "resident_prover_check")
     if os.path.exists(rp):
         try:
-            c = subprocess.run([rp, str(d), "squares"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+            c = subprocess.run([rp, str(d), "squares"], env=base_env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
             js = [l for l in c.stdout.splitlines() if l.startswith('{"resident_prover"')]
             res["resident_prover"] = dict(json.loads(js[-1])["resident_prover"], rc=c.returncode) if js else {"rc": c.returncode, "error": (c.stderr or c.stdout)[-300:]}
         except Exception as e:
@@ -226,6 +238,21 @@ def configs_summary(configs, ref_run):
     return out
 
 
+def dump_outputs(dirname, affine_pt):
+    """--dump-outputs: the last timed step's MSM result as the affine point (x, y) -- canonical integers mod p, not
+    Montgomery limbs -- in eight little-endian 32-bit limbs each, float64 (every limb exact)."""
+    import numpy as np
+    from legosnark_amd import curve
+    pt = np.asarray(affine_pt, dtype=np.uint64).reshape(3, 4)
+    rinv = pow(curve.MONT, -1, curve.P)
+    xy = np.zeros((2, 8), dtype=np.float64)
+    for row in range(2):
+        v = sum(int(pt[row, k]) << (64 * k) for k in range(4)) * rinv % curve.P
+        xy[row] = [(v >> (32 * k)) & 0xFFFFFFFF for k in range(8)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "msm_g1_affine_xy.npy"), xy)
+
+
 def being_profiled():
     """True under rocprofv3 / rocprof (their preloaded tool library): no nested profiler runs then."""
     env = os.environ
@@ -280,12 +307,19 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 PMC passes behind roofline.traffic")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (the other BASELINE.json configs)")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1: print the launch command and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline line: PMC traffic, latency, CPlink prover and host path, "
+                         "the other BASELINE.json configs, the reference's unchanged binaries, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's result to DIR/msm_g1_affine_xy.npy")
     ap.add_argument("--only-configs", default="", help="comma-separated names of legosnark_amd.benchcfg configs: run only those (the PMC child "
                                                        "passes behind a config's counter traffic use this) and print their lines")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, [a for a in sys.argv[1:] if a != "--dry-launch"]))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -306,7 +340,7 @@ def main():
     # initialises the GPU (or even imports torch)
     traffic = None
     pairing_traffic = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pmc and not args.total_log2n and args.log2n == 20 and not being_profiled():
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pmc and not args.total_log2n and args.log2n == 20 and not being_profiled():
         traffic = pmc_traffic()
         if not args.no_configs:
             # the same two counter passes for the dominant kernel of BASELINE configs[4] (2^12 fresh pairs: k_miller_fused)
@@ -318,7 +352,7 @@ def main():
     # its GPU context: a prover has the device to itself (beside a second live context every submission of the child
     # waits for the hardware scheduler: +1.5 ms, measured).
     cold_runs = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_host_path and not args.total_log2n and not being_profiled():
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_host_path and not args.total_log2n and not being_profiled():
         try:
             import subprocess
             cm = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "cold_msm.py"), "--runs", "5", "--log2n", str(args.log2n)],
@@ -341,7 +375,7 @@ def main():
 
     # ... and the reference's unchanged example binaries, for the same reason before this process has a GPU context
     ref_run = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_configs and not args.total_log2n and args.log2n == 20 and not being_profiled():
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_configs and not args.total_log2n and args.log2n == 20 and not being_profiled():
         ref_run = reference_binary_run()
 
     import numpy as np
@@ -487,7 +521,7 @@ def main():
                 dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
                 elapsed = float(tmax.item())
             got = affine_of(res.cpu().numpy().view(np.uint64))
-            return elapsed, stages, bool(np.array_equal(got, self.expected()))
+            return elapsed, stages, bool(np.array_equal(got, self.expected())), got
 
     strong = args.total_log2n > 0
     if strong:
@@ -498,24 +532,28 @@ def main():
         n = 1 << args.log2n
         n_total = world * n
         wl = Workload(n_total, rank * n, (rank + 1) * n)
-    elapsed, stages, checked = wl.timed(args.steps, args.warmup, profile=True)
+    elapsed, stages, checked, result = wl.timed(args.steps, args.warmup, profile=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
     value = n_total * args.steps / elapsed
     n_local = wl.n
     fm_per_pair = wl.B.field_mults_per_pair(wl.n)
     table_windows = wl.B.table_windows()
 
     # single-call latency (no overlap with a following call), for the record
-    lat = []
-    for _ in range(5):
-        barrier()
-        tl = time.perf_counter()
-        wl.step()
-        wl.finish()
-        lat.append(time.perf_counter() - tl)
-    latency_ms = sorted(lat)[len(lat) // 2] * 1e3
+    latency_ms = None
+    if args.full:
+        lat = []
+        for _ in range(5):
+            barrier()
+            tl = time.perf_counter()
+            wl.step()
+            wl.finish()
+            lat.append(time.perf_counter() - tl)
+        latency_ms = sorted(lat)[len(lat) // 2] * 1e3
 
     extra = {}
-    if world == 1 and not strong:
+    if args.full and world == 1 and not strong:
         # second run of SURVEY 8(d): the same bases normalised (Z = 1) must give the same point
         z1 = lsa.normalize("g1", wl.bases_jac.cpu().numpy().view(np.uint64))
         B1 = lsa.Bases("g1", z1)
@@ -530,7 +568,7 @@ def main():
     # w = (0, rF, u) (src/examples/cplink.cc:107-108).
     cplink_ms = None
     host_path = None
-    if world == 1 and not strong:
+    if args.full and world == 1 and not strong:
         N = 1 << args.log2n
         npl = N + 2
         rng = synth.Xoshiro256ss(seed=synth.SEED ^ 0xC9)
@@ -598,14 +636,14 @@ def main():
 
     # BASELINE.json configs[3] shape whenever there is more than one rank: one 2^24+2 CPlink MSM
     cplink_sharded = None
-    if world > 1 and not strong:
+    if args.full and world > 1 and not strong:
         T = int(os.environ.get("LSA_BENCH_TOTAL_LOG2N", "24"))
         nt = (1 << T) + 2
         lo, hi = lsa.shard_range(nt, world, rank)
         wl.B.close()
         del wl
         w4 = Workload(nt, lo, hi, cplink=True)
-        el4, _, ok4 = w4.timed(10, 2)
+        el4, _, ok4, _ = w4.timed(10, 2)
         cplink_sharded = {"workload": "CPlink prover MSM n=2^%d+2 split over %d GPUs (lsa_shard_range), 1 RCCL all-gather of 96-B partials" % (T, world),
                           "ms_per_prove": el4 / 10 * 1e3, "pairs_per_s": nt * 10 / el4, "result_checked": ok4, "steps": 10}
 
@@ -656,16 +694,15 @@ def main():
                                   "note": "254-bit field multiplications/s in k_accumulate vs the microbenchmarked "
                                           "ceiling of the 9x29-bit Montgomery product on this chip"}},
             "stage_ms": {k: round(v, 4) for k, v in stages.items() if k != "calls"},
-            "single_call_latency_ms": latency_ms,
-            "cplink_prover_ms": cplink_ms,
-            "cplink_prover_host_path_ms": host_path,
-            "cplink_sharded": cplink_sharded,
             "host": {"cpu_model": cpu_model(), "nproc": os.cpu_count()},
             "pipelining": "the tail (reduce+fold) of step i runs on an internal stream and overlaps the front of "
                           "step i+1; stage_ms are measured under that overlap; LSA_NO_OVERLAP=1 serialises",
         }
+        if args.full:
+            out.update({"single_call_latency_ms": latency_ms, "cplink_prover_ms": cplink_ms, "cplink_prover_host_path_ms": host_path,
+                        "cplink_sharded": cplink_sharded})
         out.update(extra)
-        if not args.no_configs and world == 1 and not strong and args.log2n == 20:
+        if args.full and not args.no_configs and world == 1 and not strong and args.log2n == 20:
             # the other BASELINE.json configs, each result-checked (a failed check carries "error" and no time)
             from legosnark_amd import benchcfg
             out["configs"] = benchcfg.measure(lsa, torch, np, dev, log2n=20, d=20, log2pairs=12, reps=5,
@@ -687,8 +724,9 @@ def main():
                 raise SystemExit("bench.py: the resident prover's proof differs from the unchanged reference prover's: %s" % rp)
         # every config once more in a few hundred bytes, close to the END of the line: whoever keeps only the tail of this
         # process's output still sees one time and one fraction per config (BENCH_r05's tail began inside the pairing entry)
-        out["configs_summary"] = configs_summary(out.get("configs") or [], ref_run)
-        if not args.no_cpu_baseline and world == 1 and not strong:
+        if args.full:
+            out["configs_summary"] = configs_summary(out.get("configs") or [], ref_run)
+        if args.full and not args.no_cpu_baseline and world == 1 and not strong:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as o   # the checker, timed as the reported CPU baseline
             ns = 1 << min(args.cpu_sample_log2, args.log2n)

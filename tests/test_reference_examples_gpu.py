@@ -1,6 +1,6 @@
 """GPU: LegoSNARK's UNCHANGED example programs, compiled against the libff-compatible shim
-(legosnark_amd/shim, built by __graft_entry__.build() in the dev container where
-/root/reference exists) and linked with the MI355X library, run end to end.
+(legosnark_amd/shim; oracle/reference.mk, run by __graft_entry__.build() where the reference's
+sources exist, builds them into oracle/_ref/) and linked with the MI355X library, run end to end.
 cplink asserts MYREQUIRE(ss.verify(...)) itself (/root/reference/src/examples/cplink.cc:114):
 prover MSM <-> keygen sparse-MSM / batch_exp <-> 3 pairings must be mutually consistent."""
 import os
@@ -10,36 +10,44 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "build", "reference")
+REF_OUT = os.path.join(ROOT, "oracle", "_ref")
+BIN = os.path.join(REF_OUT, "reference")
 
 
-CMAKE_BIN = os.path.join(ROOT, "build", "reference_cmake", "src", "examples")
+CMAKE_BIN = os.path.join(REF_OUT, "reference_cmake", "src", "examples")
 # the reference's -DMULTICORE=ON configuration (-fopenmp -DMULTICORE=1): Makefile- and CMake-built
-BIN_MC = os.path.join(ROOT, "build", "reference_mc")
-CMAKE_BIN_MC = os.path.join(ROOT, "build", "reference_cmake_mc", "src", "examples")
+BIN_MC = os.path.join(REF_OUT, "reference_mc")
+CMAKE_BIN_MC = os.path.join(REF_OUT, "reference_cmake_mc", "src", "examples")
 
 
 def require_binary(exe):
-    """The binaries are built from the reference's sources, which exist only in the dev container; build/ travels
-    with the snapshot.  tests/golden/reference_build_manifest.json (tracked, written by __graft_entry__.build())
-    lists what was built: a listed binary that is missing is a FAILURE -- lost evidence must not look like a skip.
+    """The binaries are built from the reference's sources, which only exist where the tree was built; oracle/_ref/
+    travels with the tree.  oracle/_ref/manifest.json (written by __graft_entry__.build()) lists what was built:
+    a listed binary that is missing is a FAILURE -- lost evidence must not look like a skip.
     Without a manifest (a checkout that never ran build() next to the reference) there is nothing to run."""
     if os.path.exists(exe):
         return
     import json
-    manifest = os.path.join(ROOT, "tests", "golden", "reference_build_manifest.json")
+    manifest = os.path.join(REF_OUT, "manifest.json")
     listed = []
     if os.path.exists(manifest):
         listed = json.load(open(manifest)).get("binaries", [])
     rel = os.path.relpath(exe, ROOT)
     assert rel not in listed, "%s was built by __graft_entry__.build() (manifest) but is missing from this snapshot" % rel
-    pytest.skip("%s missing and not in the build manifest: run __graft_entry__.build() where /root/reference exists" % exe)
+    pytest.skip("%s missing and not in the build manifest: run __graft_entry__.build() where the reference's sources exist" % exe)
+
+
+def binary_env(**extra_env):
+    """The binaries' run path names the directory they were linked in; they load this tree's library."""
+    lib_dir = os.path.join(ROOT, "legosnark_amd")
+    path = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib_dir + (":" + path if path else ""), **extra_env)
 
 
 def run(name, *args, seed="7", bindir=BIN, **extra_env):
     exe = os.path.join(bindir, name)
     require_binary(exe)
-    env = dict(os.environ, LSA_SEED=seed, **extra_env)
+    env = binary_env(LSA_SEED=seed, **extra_env)
     return subprocess.run([exe, *args], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
 
 
@@ -109,7 +117,7 @@ def test_verifier_side_through_the_shim_deferred_equals_call_by_call():
     for eager in ("0", "1"):
         exe = os.path.join(BIN, "pairing_check")
         require_binary(exe)
-        env = dict(os.environ, LSA_SEED="11", LSA_SHIM_EAGER=eager)
+        env = binary_env(LSA_SEED="11", LSA_SHIM_EAGER=eager)
         r = subprocess.run([exe, "6"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
         assert r.returncode == 0, r.stdout[-2000:]
         outs.append(json.loads(r.stdout.strip().splitlines()[-1]))
@@ -127,7 +135,7 @@ def test_libff_surface_the_examples_do_not_reach():
     assert "shim_check: 0 failure(s)" in r.stdout and "FAIL" not in r.stdout
 
 
-@pytest.mark.parametrize("bindir", [BIN, BIN_MC])
+@pytest.mark.parametrize("bindir", [BIN, BIN_MC], ids=["single", "multicore"])
 def test_domains_that_are_not_powers_of_two_carry_the_lipmaa_gadget(bindir):
     """legosnark_amd/shim/checks/domain_check.cc: libfqfft's step radix-2 domain (m = 2^b + 2^s) through the shim's
     evaluation_domain interface -- FFT / iFFT / cosetFFT / icosetFFT against Horner at get_domain_element(k), the Lagrange
@@ -155,7 +163,7 @@ def test_multiexpma_on_a_chunk_per_process_from_cpp(tmp_path):
     binary runs with WORLD_SIZE = N, RANK = r, LSA_DEVICE = r on an N-GPU node."""
     exe = os.path.join(BIN, "spmd_prover_check")
     require_binary(exe)
-    env = dict(os.environ, RANK="0", WORLD_SIZE="1", LSA_COMM_FILE=str(tmp_path / "comm.id"))
+    env = binary_env(RANK="0", WORLD_SIZE="1", LSA_COMM_FILE=str(tmp_path / "comm.id"))
     r = subprocess.run([exe, "12"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
     assert r.returncode == 0, r.stdout[-2000:]
     assert '"matches_single_gpu": true' in r.stdout
@@ -169,7 +177,7 @@ def test_shim_stats_and_call_trace_account_for_a_run():
     import json
     exe = os.path.join(BIN, "hadamard")
     require_binary(exe)
-    env = dict(os.environ, LSA_SEED="7", LSA_SHIM_STATS="1", LSA_TRACE="1")
+    env = binary_env(LSA_SEED="7", LSA_SHIM_STATS="1", LSA_TRACE="1")
     r = subprocess.run([exe, "8"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stderr.splitlines() if l.startswith('{"lsa_shim_stats"')]

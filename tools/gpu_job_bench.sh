@@ -4,6 +4,7 @@ cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 TAG=${TAG:-r04}
 export TMPDIR=/tmp
+set -- --full "$@"          # the digest below reads what only a --full line carries
 t0=$(date +%s.%N)
 python bench.py "$@" > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
 rc=$?

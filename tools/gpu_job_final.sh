@@ -9,7 +9,7 @@ OUT=$(pwd)/gpurun_out
 mkdir -p "$OUT"
 python -m pytest tests -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3 > "$OUT/${TAG}_gpu_tests.log"
 cat "$OUT/${TAG}_gpu_tests.log"
-python bench.py > "$OUT/${TAG}_bench_default.json" 2> "$OUT/${TAG}_bench_stderr.txt"
+python bench.py --full > "$OUT/${TAG}_bench_default.json" 2> "$OUT/${TAG}_bench_stderr.txt"
 python3 - <<PY
 import json
 d=json.loads(open("$OUT/${TAG}_bench_default.json").read().strip().splitlines()[-1])

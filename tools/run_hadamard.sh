@@ -5,8 +5,10 @@
 # under rocprofv3 --kernel-trace (program directly after --) with the per-kernel summary next to it.
 TAG=${TAG:-r03}
 # the binary the reference's own CMakeLists.txt builds (its flags, -O3 -ggdb) when it is there, else the Makefile build
-HAD=build/reference_cmake/src/examples/hadamard
-[ -x "$HAD" ] || HAD=build/reference/hadamard
+HAD=oracle/_ref/reference_cmake/src/examples/hadamard
+[ -x "$HAD" ] || HAD=oracle/_ref/reference/hadamard
+# built elsewhere (oracle/reference.mk): the library is this tree's
+export LD_LIBRARY_PATH=$(pwd)/legosnark_amd${LD_LIBRARY_PATH:+:$LD_LIBRARY_PATH}
 export TMPDIR=/tmp
 OUT=$(pwd)/gpurun_out
 mkdir -p "$OUT"
