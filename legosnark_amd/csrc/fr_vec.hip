@@ -771,14 +771,20 @@ static FusedPass fused_pass(size_t avail, unsigned want) {
     p.blocks = (size_t)1 << (avail - p.bl);
     return p;
 }
+__global__ __launch_bounds__(64) void k_fr_clear_one(Fr *p) {
+    if (threadIdx.x == 0) *p = Fr::zero();
+}
 static int fr_cppoly_fold_issue(const Fr *d_v, size_t d, const Fr *d_r, Fr *d_w, Fr *d_tmp, hipStream_t st);
 int fr_cppoly_fold_device(const Fr *d_v, size_t d, const Fr *d_r, Fr *d_w, Fr *d_tmp, hipStream_t st) {
     return fold_run(1, d, d_v, d_r, d_w, d_tmp, nullptr, st, [=](hipStream_t s) { return fr_cppoly_fold_issue(d_v, d, d_r, d_w, d_tmp, s); });
 }
 static int fr_cppoly_fold_issue(const Fr *d_v, size_t d, const Fr *d_r, Fr *d_w, Fr *d_tmp, hipStream_t st) {
     const size_t N = (size_t)1 << d;
-    HIPCHK(hipMemsetAsync(d_w + (N - 1), 0, sizeof(Fr), st));
-    if (d == 0) return LSA_OK;
+    // the value-initialised last entry, by a kernel: as a hipMemsetAsync this became a memset node of the captured graph
+    // (fold_run) whose fill value did not survive replays -- w[N - 1] came back as 16 bytes of stale host memory written
+    // twice whenever the destination did not already hold zeros (tests/test_fr_vec_gpu.py: ..._on_every_replay)
+    hipLaunchKernelGGL(k_fr_clear_one, dim3(1), dim3(64), 0, st, d_w + (N - 1));
+    if (d == 0) { HIPCHK(hipGetLastError()); return LSA_OK; }
     const Fr *src = d_v;
     Fr *bufA = d_tmp, *bufB = d_tmp + (N >> 1);
     size_t start = 0, i = 0;

@@ -141,8 +141,8 @@ LSA_HD Inv256 inv_mod_p(const Inv256 &y) {
             f0 -= f1 & (int64_t)odd;
             g0 -= g1 & (int64_t)odd;
             ah >>= 1;
-            f1 <<= 1;
-            g1 <<= 1;
+            f1 = (int64_t)((uint64_t)f1 << 1);                  // f1, g1 may be negative: << on a negative value is undefined in C++17
+            g1 = (int64_t)((uint64_t)g1 << 1);
         }
         // ---- apply the matrix to (a, b) and (u, v)
         uint32_t f0s = (uint32_t)(f0 >> 63), g0s = (uint32_t)(g0 >> 63), f1s = (uint32_t)(f1 >> 63), g1s = (uint32_t)(g1 >> 63);

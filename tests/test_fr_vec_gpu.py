@@ -23,6 +23,33 @@ def test_cppoly_witness_vs_oracle(lsa, d):
     assert not got[-1].any()                       # value-initialised tail entry (poly.h:52)
 
 
+@pytest.mark.parametrize("d", [9, 13, 16])
+def test_cppoly_witness_zeroes_its_last_entry_on_every_replay(lsa, d):
+    """The recursion writes 2^d - 1 coefficients and must zero w[2^d - 1] itself, on the first call (which captures the
+    launch sequence as a graph, d >= 8) and on every replay of it.  Found by tests/fuzz_parity.py run as a script (master
+    seed 1, cases 783389906492 / 161720252498 / 660338114421 of fr_fold): after calls that had churned the host heap, w[-1]
+    came back as a 16-byte pattern of stale host memory written twice -- the fill value of the captured memset node did not
+    survive replays -- and only a destination that did not already hold zeros shows it.  So: w pre-filled with ones, host
+    allocations between the calls, the same buffers every time."""
+    import torch
+    N = 1 << d
+    v, _ = o.random_scalars(N, seed=1300 + d)
+    r, _ = o.random_scalars(d, seed=1400 + d)
+    want = o.fr_cppoly_witness(v, r)
+    d_v = torch.from_numpy(v.view(np.int64)).to("cuda:0")
+    d_r = torch.from_numpy(r.view(np.int64)).to("cuda:0")
+    d_w = torch.empty((N, 4), dtype=torch.int64, device="cuda:0")
+    for rep in range(8):
+        d_w.fill_(-1)
+        torch.cuda.synchronize()
+        junk = [np.full(1 + (7 * rep + i) % 61, 0x7BD64E4DD500 + i, dtype=np.uint64) for i in range(4000)]    # host heap traffic
+        del junk
+        lsa.cppoly_witness(d_v, d_r, out=d_w)
+        got = d_w.cpu().numpy().view(np.uint64)
+        assert not got[-1].any(), (d, rep, [hex(int(x)) for x in got[-1]])
+        assert np.array_equal(got, want), (d, rep)
+
+
 @pytest.mark.parametrize("d", [0, 1, 2, 7, 9, 10, 11, 12, 13, 14, 15, 16, 18, 20, 21, 22])
 def test_eval_mle_vs_oracle(lsa, d):
     v, _ = o.random_scalars(1 << d, seed=500 + d)

@@ -61,6 +61,56 @@ def test_host_64_bit_limbs_agree_with_the_device_limbs(tmp_path):
     assert outs[0] == outs[1] and outs[0].count("inv ") == 2
 
 
+# ---- the same programs under AddressSanitizer + UndefinedBehaviorSanitizer ------------------------------------------
+# The headers under csrc/ are device code as well: what is undefined behaviour on the host (a shift of a negative value,
+# an out-of-range index into a limb array) is undefined in the kernels too, where nothing reports it.  Pure host code
+# only: the two programs that link the HIP library (test_shim_io.cc, test_shim_domains.cc) stay out of this tier.
+SANITIZE = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core"]
+_COLS = ["-DLSA_FP29_COLS", "-DLSA_F29_COLS", "-DLSA_FR29_COLS"]
+SANITIZED_PROGRAMS = ([(n, n, []) for n in _HEADER_TESTS]
+                      + [(n + "_cols", n, _COLS) for n in ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core"]]
+                      + [(n + "_32", n, ["-DLSA_FP_HOST32"]) for n in ["test_fp29", "test_glv", "test_tower29"]]
+                      + [("test_fp_host_64", "test_fp_host", []), ("test_fp_host_32", "test_fp_host", ["-DLSA_FP_HOST32"])])
+
+
+@pytest.fixture(scope="module")
+def sanitizer_toolchain(tmp_path_factory):
+    """Skips only where a one-line program does not LINK with the sanitizer flags (no runtime libraries installed)."""
+    d = tmp_path_factory.mktemp("sanitizer_probe")
+    src = d / "probe.cc"
+    src.write_text("int main() { return 0; }\n")
+    r = subprocess.run(["g++", *SANITIZE, str(src), "-o", str(d / "probe")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        pytest.skip("g++ cannot link with -fsanitize=address,undefined here: " + r.stdout[-300:])
+
+
+@pytest.mark.parametrize("tag,name,defines", SANITIZED_PROGRAMS, ids=[p[0] for p in SANITIZED_PROGRAMS])
+def test_host_cpp_sanitized(tag, name, defines, tmp_path, sanitizer_toolchain):
+    """Every program of this file again with ASan + UBSan, any report fatal: exit status 0 and PASS."""
+    src = os.path.join(ROOT, "tests", "cpp", name + ".cc")
+    exe = str(tmp_path / (tag + "_san"))
+    subprocess.check_call(["g++", *SANITIZE, *defines, "-I", os.path.join(ROOT, "legosnark_amd", "csrc"), src, "-o", exe])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0 and "PASS" in r.stdout, r.stdout[-3000:]
+
+
+def test_oracle_under_ubsan_passes_the_cpu_vector_tests(tmp_path, sanitizer_toolchain):
+    """oracle/bn254.c is the checker of every parity test: built with UBSan (any report fatal) it must still pass its own
+    golden vectors and the public EVM vectors.  A child pytest loads that build through LSA_ORACLE_LIB (oracle_lib.build).
+    UBSan only: ASan inside a library loaded by an uninstrumented interpreter would need its runtime preloaded."""
+    import sys
+    so = str(tmp_path / "liboracle_bn254_ubsan.so")
+    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-fPIC", "-fsanitize=undefined", "-fno-sanitize-recover=all", "-shared",
+                           "-o", so, os.path.join(ROOT, "oracle", "bn254.c"), "-lpthread"])
+    env = dict(os.environ, LSA_ORACLE_LIB=so)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "not gpu", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_oracle_golden.py"), os.path.join(ROOT, "tests", "test_public_vectors.py")],
+                       cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1800)
+    assert r.returncode == 0 and " passed" in r.stdout and "failed" not in r.stdout and "skipped" not in r.stdout, r.stdout[-3000:]
+    assert "runtime error" not in r.stdout
+
+
 def test_frobenius_row_constants_are_the_generators_output():
     """csrc/frob_rows.h is generated (tools/gen_frob_rows.py: the Frobenius factors of bn254_constants.h multiplied out,
     conjugation and signs folded in, 29-bit-limb Montgomery form); the committed table must be what the script prints,
