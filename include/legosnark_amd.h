@@ -314,6 +314,42 @@ int lsa_fr_ntt(void *a_mont, size_t log_n, const void *omega_mont, int inverse, 
  * libff::get_root_of_unity(2^(big_log + 1))).  inverse / coset_g / on_device as for lsa_fr_ntt. */
 int lsa_fr_ntt_step(void *a_mont, size_t big_log, size_t small_log, const void *omega_mont, int inverse, const void *coset_g_mont, int on_device);
 
+/* The Lipmaa Hadamard prover's quotient polynomial (CPHadL::prove, src/gadgets/lipmaa.cc:103-176: coefficients_for_H, the
+ * scalar vector of its MSM) from the three committed vectors, all on the device:
+ *     H = d2 A + d1 B - d3 + d1 d2 Z + (A B - C) / Z,       equivalently  H Z = (A + d1 Z)(B + d2 Z) - (C + d3 Z),
+ * A, B, C the interpolants of a, b, c on the domain and Z the domain's monic vanishing polynomial.
+ *   Domain: small_log < 0 -- the basic radix-2 domain, m = 2^big_log, 1 <= big_log <= 28, omega as for lsa_fr_ntt,
+ *           Z = x^m - 1;  otherwise libfqfft's step radix-2 domain, m = 2^big_log + 2^small_log, omega and the limits as
+ *           for lsa_fr_ntt_step, Z = (x^(2^big_log) - 1)(x^(2^small_log) - omega^(2^small_log)).
+ *   a, b, c: n <= m values each on the domain's points in the domain's order; entries n .. m-1 count as zero (the
+ *           reference's zero-filled vectors).  Not modified.
+ *   d123:   HOST, three Fr: the commitment randomness d1, d2, d3 of a, b, c.
+ *   coset_g: HOST, one Fr: the coset on which the division by Z happens (the reference: Fr::multiplicative_generator).  A
+ *           coset on which Z may vanish is refused before any device work: coset_g^m = 1 on the basic domain,
+ *           coset_g^(2 * 2^big_log) = 1 on the step domain.
+ *   h_out:  m + 1 Fr, lowest degree first; must not overlap the inputs.
+ * NOTE: the reference fills aB from aPts (lipmaa.cc:121), so ITS proofs are those of this call with b == a; b is a
+ * separate argument here.
+ * Three iFFTs, three coset FFTs, one pointwise kernel, one inverse coset FFT (csrc/fr_poly.hip), on grow-only staging
+ * owned by the library (two vectors, the transforms' scratch; for host callers a third): no allocation per call after
+ * the first of a size.  Fr values are canonical, so the bytes are those of the reference's schedule.
+ * on_device != 0: a, b, c, h_out are device pointers and the call is asynchronous on lsa_stream(), with no host
+ * synchronisation inside: h_out can go straight to lsa_msm_run_async as the scalar vector.  (Two things the call shares
+ * with lsa_fr_ntt do wait for the device when they happen: the first call of a larger size grows the staging, and a
+ * domain whose twiddle tables were evicted from ntt.hip's cache frees the evicted ones -- a prover that keeps to its
+ * sizes and domains meets neither after its first proof.)  Else host pointers and a
+ * blocking call.  LSA_ERR_INVALID: null argument, n > m, big_log / small_log out of range, refused coset. */
+int lsa_fr_hadamard_quotient(const void *a_mont, const void *b_mont, const void *c_mont, size_t n, size_t big_log, int small_log,
+                             const void *omega_mont, const void *coset_g_mont, const void *d123_mont, void *h_out_mont, int on_device);
+
+/* out[i] = L_i(t), i < m: evaluation_domain::evaluate_all_lagrange_polynomials(t) of the same two domains (the key
+ * generator's row, src/prototools/interp.h:68-71); big_log, small_log, omega as above.  For t a point of the domain the
+ * unit vector.  omega, t: HOST, one Fr each.  The m denominators are inverted in runs of consecutive elements, one run and
+ * one field inversion per GPU lane (csrc/fr_batch_inv.h; 16 elements: the fastest of 8, 16 and 32 measured at m = 2^20 and
+ * 2^20 + 2^19): no serial chain over the vector.
+ * on_device != 0: out is a device pointer and the call is asynchronous on lsa_stream(); else a host pointer, blocking. */
+int lsa_fr_lagrange(size_t big_log, int small_log, const void *omega_mont, const void *t_mont, void *out_mont, int on_device);
+
 /* ---- pairing ---------------------------------------------------------------------------- */
 /* out[i] = miller_loop(precompute_G1(P_i), precompute_G2(Q_i)), i < n: replaces libff
  * alt_bn128_pp::precompute_G1 / precompute_G2 / miller_loop (src/utils/globl.h:96-102,

@@ -103,6 +103,9 @@ def lib():
         L.lsa_fr_fold.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_ntt.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.lsa_fr_ntt_step.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.lsa_fr_hadamard_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int]
+        L.lsa_fr_lagrange.argtypes = [C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_sumcheck_round.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_scale_upper.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_eq_table.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int]
@@ -654,6 +657,63 @@ def fr_ntt_step(a, big_log, small_log, omega, inverse=False, coset=None):
     _after_torch(a)
     _check(lib().lsa_fr_ntt_step(_ptr(a), big_log, small_log, _host_ptr(omega), 1 if inverse else 0, _host_ptr(cg) if cg is not None else None, 1))
     return a
+
+
+def _fr_vec_len(x):
+    return x.numel() * x.element_size() // 32
+
+
+def fr_hadamard_quotient(a, b, c, d123, big_log, small_log=None, omega=None, coset=None, out=None):
+    """The Lipmaa Hadamard prover's quotient polynomial (CPHadL::prove's coefficients_for_H):
+    H = d2 A + d1 B - d3 + d1 d2 Z + (A B - C) / Z on the basic radix-2 domain of 2^big_log points (small_log None) or the
+    step domain of 2^big_log + 2^small_log points, m + 1 coefficients.  a, b, c: n <= m values each (the rest counts as
+    zero); d123: the three commitment randomnesses; omega: the domain's root of unity as for fr_ntt / fr_ntt_step; coset:
+    the coset generator (the reference: Fr::multiplicative_generator).  numpy in -> a new numpy array; torch CUDA tensors
+    in -> a torch CUDA tensor (`out`, or a new one), asynchronous on the library's stream."""
+    if omega is None or coset is None:
+        raise ValueError("fr_hadamard_quotient: omega and coset are required")
+    omega = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+    cg = np.ascontiguousarray(coset, dtype=np.uint64).reshape(4)
+    d123 = np.ascontiguousarray(d123, dtype=np.uint64).reshape(3, 4)
+    sl = -1 if small_log is None else int(small_log)
+    m = (1 << big_log) + ((1 << sl) if sl >= 0 else 0)
+    if isinstance(a, np.ndarray):
+        a, b, c = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (a, b, c))
+        if not len(a) == len(b) == len(c):
+            raise ValueError("fr_hadamard_quotient: a, b, c must have the same length")
+        h = np.zeros((m + 1, 4), dtype=np.uint64)
+        _check(lib().lsa_fr_hadamard_quotient(_host_ptr(a), _host_ptr(b), _host_ptr(c), len(a), big_log, sl, _host_ptr(omega), _host_ptr(cg),
+                                              _host_ptr(d123), _host_ptr(h), 0))
+        return h
+    n = _fr_vec_len(a)
+    if not n == _fr_vec_len(b) == _fr_vec_len(c):
+        raise ValueError("fr_hadamard_quotient: a, b, c must have the same length")
+    if out is None:
+        import torch
+        out = torch.empty((m + 1, 4), dtype=torch.int64, device=a.device)
+    elif _fr_vec_len(out) < m + 1:
+        raise ValueError("fr_hadamard_quotient: out needs %d entries" % (m + 1))
+    _after_torch(a, b, c, out)
+    _check(lib().lsa_fr_hadamard_quotient(_ptr(a), _ptr(b), _ptr(c), n, big_log, sl, _host_ptr(omega), _host_ptr(cg), _host_ptr(d123), _ptr(out), 1))
+    return out
+
+
+def fr_lagrange(big_log, small_log, omega, t, out=None):
+    """evaluate_all_lagrange_polynomials(t) of the basic radix-2 domain (small_log None) or the step domain: m Fr.  Returns a
+    new numpy array, or fills the torch CUDA tensor `out` (asynchronous on the library's stream)."""
+    omega = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+    t = np.ascontiguousarray(t, dtype=np.uint64).reshape(4)
+    sl = -1 if small_log is None else int(small_log)
+    m = (1 << big_log) + ((1 << sl) if sl >= 0 else 0)
+    if out is None:
+        res = np.zeros((m, 4), dtype=np.uint64)
+        _check(lib().lsa_fr_lagrange(big_log, sl, _host_ptr(omega), _host_ptr(t), _host_ptr(res), 0))
+        return res
+    if _fr_vec_len(out) < m:
+        raise ValueError("fr_lagrange: out needs %d entries" % m)
+    _after_torch(out)
+    _check(lib().lsa_fr_lagrange(big_log, sl, _host_ptr(omega), _host_ptr(t), _ptr(out), 1))
+    return out
 
 
 def sum_async(group, d_pts, n, d_out):

@@ -729,6 +729,7 @@ static void release_stage_buffers() {
     ntt_release();                                   // the per-domain twiddle tables (ntt.hip)
     fr_vec_release();                                // the cached hipGraphs of the Fr recursions (fr_vec.hip)
     pairing_release();
+    fr_poly_release();
 }
 
 // ---------------------------------------------------------------- CRS cache behind lsa_g1_msm / lsa_g2_msm

@@ -47,6 +47,7 @@ struct CallTrace {
 #define LSA_TRACE_CALL(name, items) CallTrace trace_scope_((name), (size_t)(items))
 void comm_release();               // comm.hip: called by lsa_shutdown
 void pairing_release();            // capi_pairing.hip: staging buffers and the G2 line-table cache
+void fr_poly_release();            // fr_poly.hip: staging buffers of the Lipmaa quotient and the Lagrange row
 
 // grow-only device staging buffer of the host-buffer entry points (the libff shim calls them
 // thousands of times with tiny inputs: no hipMalloc / hipFree per call)
