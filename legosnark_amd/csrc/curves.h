@@ -16,16 +16,18 @@ struct CurveG1 {
     using Acc = XYZZ29;
     static constexpr bool GLV = true;     // scalars split as k1 + k2*lambda (glv.h)
     static __device__ __forceinline__ Acc inf() { return Acc::inf(); }
+    // acc + (+-)[phi](b): the sign goes into the addition's own carry pass, never into a negated copy of the base
+    // (fp29.h: xyzz29_madd_signed).  ENDO = false: a caller whose entries never carry the endo bit.
+    template <bool ENDO = true>
     static __device__ __forceinline__ Acc madd(const Acc &a, const Base &b, bool negate, bool endo) {
-        Aff29 q = unpack_affine(b);
-        if (q.is_inf()) return a;
-        if (negate) q.y = sub_k<1>(F29::zero(), q.y);                  // p - y
-        if (endo) {                                                     // phi(x,y) = (beta*x, y)
-            constexpr uint32_t BETA29[9] = {0x0a337995u, 0x158d1d23u, 0x189c9b98u, 0x12fa4e45u, 0x185faadcu,
-                                            0x0176f16du, 0x0eed93bau, 0x14291140u, 0x000c0afeu};
-            q.x = mul(q.x, F29::from_limbs(BETA29));                    // [<2p; tight]
-        }
-        return xyzz29_madd(a, q);
+        return g1_madd_packed<ENDO>(a, b, negate, endo);
+    }
+    // the head of a bucket list, two finite bases, as affine + affine (4M + 2S instead of two mixed additions from infinity)
+    static constexpr bool HEAD = true;
+    static __device__ __forceinline__ bool head_ok(const Base &b0, const Base &b1) { return !packed_is_inf(b0) && !packed_is_inf(b1); }
+    template <bool ENDO = true>
+    static __device__ __forceinline__ Acc madd_head(const Base &b0, bool neg0, bool endo0, const Base &b1, bool neg1, bool endo1) {
+        return g1_madd_head<ENDO>(b0, neg0, endo0, b1, neg1, endo1);
     }
     static __device__ __forceinline__ Acc add(const Acc &a, const Acc &b) { return xyzz29_add(a, b); }
     static __device__ __forceinline__ Acc dbl(const Acc &a) { return xyzz29_dbl(a); }
@@ -55,6 +57,9 @@ struct CurveG2 {
     using Acc = XYZZ29x2;
     static constexpr bool GLV = false;
     static __device__ __forceinline__ Acc inf() { return Acc::inf(); }
+    static constexpr bool HEAD = false;      // no affine + affine head of a bucket list (CurveG1 has one)
+    // ENDO is unused here (G2 has no endomorphism entries): it only lets accumulate_body write C::template madd<ENDO> for both curves
+    template <bool ENDO = true>
     static __device__ __forceinline__ Acc madd(const Acc &a, const Base &b, bool negate, bool /*endo*/) {
         Aff29x2 q = unpack_affine(b);
         if (q.is_inf()) return a;

@@ -206,7 +206,8 @@ struct F29 {
     }
     // (a0*b0 + a1*b1) / 2^261 mod p with ONE reduction: both products accumulate in the same
     // 64-bit columns.  Needs a0*b0 + a1*b1 < 169 p^2 and at most one loose operand per
-    // product (18*2^59 + 9*2^58 < 2^64).  [< 2p; tight]
+    // product (18*2^59 + 9*2^58 < 2^64); or one sub_loose difference (limbs < 3 * 2^29) per product beside a TIGHT partner
+    // (54 * 2^58 + 9 * 2^58 + carry < 2^64, see sub_loose).  [< 2p; tight]
     friend LSA_HD F29 dot2(const F29 &a0, const F29 &b0, const F29 &a1, const F29 &b1) {
 #if defined(LSA_FP29_COLS)
         {
@@ -416,9 +417,56 @@ LSA_HD F29 sub_k(const F29 &a, const F29 &b) {
     return r;
 }
 
+// (+-)s - b + K*p with ONE carry pass: m (an lsa_mask: all ones / zero) negates s inside it.  For tight s,
+//     -s = sum_{i<8} (s_i ^ MASK) * 2^(29 i)  +  (~s_8) * 2^232  +  1
+// (complement every limb within its width; the 1 enters as the carry into limb 0), so the sign costs one XOR per limb.
+// Requires s tight and (+-)s - b + K*p > 0 for both signs; limbs stay within int32 as in sub_k.  [(+-)s - b + Kp; tight]
+template <int K>
+LSA_HD F29 sub_k_signed(const F29 &s, const F29 &b, uint32_t m) {
+    F29 r;
+    uint64_t pc = 0;
+    const uint32_t m29 = m & F29::MASK;
+    int32_t c = (int32_t)(m & 1u);
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        pc += (uint64_t)F29::p(i) * (uint32_t)K;
+        uint32_t kp = (i < 8) ? ((uint32_t)pc & F29::MASK) : (uint32_t)pc;
+        pc >>= 29;
+        int32_t v = (int32_t)(s.l[i] ^ (i < 8 ? m29 : m)) + (int32_t)kp - (int32_t)b.l[i] + c;
+        if (i < 8) { r.l[i] = (uint32_t)v & F29::MASK; c = v >> 29; }
+        else r.l[i] = (uint32_t)v;
+    }
+    return r;
+}
+
+// a - b + K*p WITHOUT a carry pass, for an operand of dot2 / mul whose partner is tight.  K*p is taken in the
+// redundant limbs  c_0 = (Kp)_0 + 2^29,  c_i = (Kp)_i + 2^29 - 1 (0 < i < 8),  c_8 = (Kp)_8 - 1  (the same value: every
+// limb but the top one borrows 2^29 from the one above), so that no limb of the difference is negative:
+//   requires a, b tight and b < (K-1)*p (then b_8 <= ((K-1)p)_8 <= (Kp)_8 - 1);
+//   result limbs  0 <= a_i - b_i + c_i <= 3 * 2^29 - 2  (i < 8),  top limb <= a_8 + (Kp)_8 - 1.   [a - b + Kp; limbs < 3 * 2^29]
+// Column bound of dot2 with ONE such operand in EACH product and tight partners: 2 * 9 * (2^29 * 3 * 2^29) = 54 * 2^58, plus
+// 9 * 2^58 for the m * p terms and a carry < 2^36: < 63.1 * 2^58 < 2^64.  With the limbs the constants really have (and the
+// small top limbs) the largest column at the two call sites is 35.1 * 2^58: tests/cpp/test_g1_madd_peeled.cc computes
+// it in 128-bit integers and asserts the limit.
+template <int K>
+LSA_HD F29 sub_loose(const F29 &a, const F29 &b) {
+    F29 r;
+    uint64_t pc = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        pc += (uint64_t)F29::p(i) * (uint32_t)K;
+        const uint32_t kp = (i < 8) ? ((uint32_t)pc & F29::MASK) : (uint32_t)pc;
+        pc >>= 29;
+        const uint32_t c = (i == 0) ? kp + (1u << 29) : (i < 8) ? kp + F29::MASK : kp - 1u;
+        r.l[i] = a.l[i] + c - b.l[i];
+    }
+    return r;
+}
+
 // ------------------------------------------------------------------------------------
 // points over F29.  Invariants of an accumulator (X,Y,ZZ,ZZZ), all limbs tight:
 //     X < 8p,  Y < 4p,  ZZ < 2p,  ZZZ < 2p;  infinity <=> ZZ has all limbs zero.
+// Infinity is only ever written as XYZZ29::inf(), ALL FOUR coordinates literal zeros (xyzz29_madd_signed relies on X and Y).
 // Bases (x,y) are canonical (< p); (0,0) encodes infinity.
 // ------------------------------------------------------------------------------------
 struct Aff29 {
@@ -464,7 +512,8 @@ LSA_HD XYZZ29 xyzz29_dbl(const XYZZ29 &a) {
     return {X3, Y3, mul(V, a.ZZ), mul(W, a.ZZZ)};
 }
 
-// acc + (x2,y2), complete (madd-2008-s).  The hot operation: 8M + 2S, ~2300 instructions.
+// acc + (x2,y2), complete (madd-2008-s): 8M + 2S.  The plain form (smul.h, the host tests' yardstick); the bucket
+// accumulation runs xyzz29_madd_signed below.
 LSA_HD XYZZ29 xyzz29_madd(const XYZZ29 &a, const Aff29 &b) {
     if (b.is_inf()) return a;
     if (a.is_inf()) return {b.x, b.y, F29::one(), F29::one()};
@@ -482,6 +531,56 @@ LSA_HD XYZZ29 xyzz29_madd(const XYZZ29 &a, const Aff29 &b) {
     F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));          // R^2 - PPP - 2Q + 6p  [<8p]
     F29 Y3 = dot2(R, sub_k<8>(Q, X3), sub_k<4>(F29::zero(), a.Y), PPP);   // R(Q-X3) + (4p-Y1)PPP: 60 + 8  [<2p]
     return {X3, Y3, mul(a.ZZ, PP), mul(a.ZZZ, PPP)};
+}
+
+// The bucket accumulation's mixed addition: acc + s * (x2, y2) with the sign s = -1 where m (an lsa_mask) is all ones, and
+// (x2, y2) the STORED base, which must not be infinity (x2 < 2p, y2 < p, tight).  Same formulas as xyzz29_madd; what differs:
+//  - y2 enters only through S2, so the sign is applied to S2 inside the carry pass that forms R (sub_k_signed), with
+//    6p covering the worse sign: R = (+-)S2 - Y1 + 6p in (0, 8p);
+//  - (Q - X3) and (-Y1), each multiplied by a tight partner in dot2, skip their carry passes (sub_loose);
+//  - no test of acc for infinity ahead of the products: acc = inf() is all zeros, so U2 = S2 = 0, Pd = 8p, R = 6p and the
+//    rare path below (Pd == 0 mod p) sorts it out together with doubling and cancellation.
+LSA_HD XYZZ29 xyzz29_madd_rare(const XYZZ29 &a, const Aff29 &b, uint32_t m, const F29 &R) {
+    Aff29 q = b;
+    if (m) q.y = sub_k<1>(F29::zero(), b.y);       // p - y
+    if (a.is_inf()) return {q.x, q.y, F29::one(), F29::one()};
+    if (R.is_zero_mod_p()) return xyzz29_dbl_affine(q);
+    return XYZZ29::inf();
+}
+LSA_HD XYZZ29 xyzz29_madd_signed(const XYZZ29 &a, const Aff29 &b, uint32_t m) {
+    F29 U2 = mul(b.x, a.ZZ);                       // [<2p]
+    F29 S2 = mul(b.y, a.ZZZ);                      // [<2p]  (of the stored y)
+    F29 Pd = sub_k<8>(U2, a.X);                    // U2 - X1 + 8p      [<10p]
+    F29 R = sub_k_signed<6>(S2, a.Y, m);           // (+-)S2 - Y1 + 6p  [<8p]
+    if (Pd.is_zero_mod_p()) return xyzz29_madd_rare(a, b, m, R);
+    F29 PP = sqr(Pd);
+    F29 PPP = mul(Pd, PP);
+    F29 Q = mul(a.X, PP);
+    F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));          // R^2 - PPP - 2Q + 6p  [<8p]
+    // R(Q - X3 + 10p) + (6p - Y1)PPP: 8 * 12 + 6 * 2 = 108 p^2 < 169 p^2  [<2p];  X3 < 8p <= 9p and Y1 < 4p <= 5p (sub_loose)
+    F29 Y3 = dot2(R, sub_loose<10>(Q, X3), sub_loose<6>(F29::zero(), a.Y), PPP);
+    return {X3, Y3, mul(a.ZZ, PP), mul(a.ZZZ, PPP)};
+}
+
+// (x1, y1) + s * (x2, y2), both affine and neither infinity: the head of a bucket list.  With ZZ1 = ZZZ1 = 1 the four
+// products by one drop out of the mixed addition: 4M + 2S.  (x1, y1) carries its own sign already (x1 < 2p, y1 <= p,
+// tight); (x2, y2) is the stored base and m its sign as in xyzz29_madd_signed.  Output within the accumulator invariants.
+LSA_HD XYZZ29 xyzz29_add_affine(const Aff29 &a, const Aff29 &b, uint32_t m) {
+    F29 Pd = sub_k<2>(b.x, a.x);                   // x2 - x1 + 2p      [<4p]
+    F29 R = sub_k_signed<2>(b.y, a.y, m);          // (+-)y2 - y1 + 2p  [<3p]  (> 0: y2 < p, y1 <= p)
+    if (Pd.is_zero_mod_p()) {
+        if (!R.is_zero_mod_p()) return XYZZ29::inf();
+        Aff29 q = b;
+        if (m) q.y = sub_k<1>(F29::zero(), b.y);
+        return xyzz29_dbl_affine(q);
+    }
+    F29 PP = sqr(Pd);
+    F29 PPP = mul(Pd, PP);
+    F29 Q = mul(a.x, PP);
+    F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));          // [<8p]
+    // R(Q - X3 + 10p) + (3p - y1)PPP: 3 * 12 + 3 * 2 = 42 p^2  [<2p];  y1 <= p < 2p (sub_loose)
+    F29 Y3 = dot2(R, sub_loose<10>(Q, X3), sub_loose<3>(F29::zero(), a.y), PPP);
+    return {X3, Y3, PP, PPP};
 }
 
 // a + b, complete (add-2008-s).  Inputs and output within the accumulator invariants.
@@ -504,6 +603,39 @@ LSA_HD XYZZ29 xyzz29_add(const XYZZ29 &a, const XYZZ29 &b) {
     F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));
     F29 Y3 = dot2(R, sub_k<8>(Q, X3), sub_k<2>(F29::zero(), S1), PPP);    // R(Q-X3) + (2p-S1)PPP: 40 + 4  [<2p]
     return {X3, Y3, mul(mul(a.ZZ, b.ZZ), PP), mul(mul(a.ZZZ, b.ZZZ), PPP)};
+}
+
+// ---- the two operations of the G1 bucket accumulation on packed, stored bases (curves.h: CurveG1) ----
+// ENDO = false compiles the endomorphism out (the wide path never sets an entry's endo bit).
+LSA_HD bool packed_is_inf(const AffPacked &q) {
+    if ((q.x[0] | q.y[0]) != 0) return false;      // all a finite base pays, but for 2^-64 of them
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 1; i < 8; i++) o |= q.x[i] | q.y[i];
+    return o == 0;
+}
+template <bool ENDO>
+LSA_HD Aff29 g1_unpack_base(const AffPacked &b, bool endo) {
+    Aff29 q = unpack_affine(b);
+    if (ENDO && endo) {                                                 // phi(x,y) = (beta*x, y)
+        constexpr uint32_t BETA29[9] = {0x0a337995u, 0x158d1d23u, 0x189c9b98u, 0x12fa4e45u, 0x185faadcu,
+                                        0x0176f16du, 0x0eed93bau, 0x14291140u, 0x000c0afeu};
+        q.x = mul(q.x, F29::from_limbs(BETA29));                        // [<2p; tight]
+    }
+    return q;
+}
+// acc + (+-)[phi](base)
+template <bool ENDO>
+LSA_HD XYZZ29 g1_madd_packed(const XYZZ29 &a, const AffPacked &b, bool negate, bool endo) {
+    if (packed_is_inf(b)) return a;
+    return xyzz29_madd_signed(a, g1_unpack_base<ENDO>(b, endo), lsa_mask(negate ? ~0u : 0u));
+}
+// (+-)[phi](b0) + (+-)[phi](b1), neither infinity: the first two entries of a bucket list
+template <bool ENDO>
+LSA_HD XYZZ29 g1_madd_head(const AffPacked &b0, bool neg0, bool endo0, const AffPacked &b1, bool neg1, bool endo1) {
+    Aff29 q0 = g1_unpack_base<ENDO>(b0, endo0);
+    if (neg0) q0.y = sub_k<1>(F29::zero(), q0.y);                       // p - y  [<=p]
+    return xyzz29_add_affine(q0, g1_unpack_base<ENDO>(b1, endo1), lsa_mask(neg1 ? ~0u : 0u));
 }
 
 LSA_HD XYZZ29 xyzz29_neg(const XYZZ29 &a) {

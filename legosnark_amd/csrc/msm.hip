@@ -951,7 +951,8 @@ __global__ __launch_bounds__(256) void k_size_scatter(const uint32_t *__restrict
 // kernel 4: bucket accumulation (one lane per bucket); heavy buckets deferred.
 // C = curve traits (CurveG1: 29-bit limbs, 64-B packed bases; CurveG2: Fq2 on the same limbs, 128-B bases).
 // The next entry's point is fetched before the current mixed add is issued, so the
-// ~2 us gather latency hides under ~2300 VALU instructions of arithmetic.
+// ~2 us gather latency hides under the ~2300 VALU instructions of a mixed addition (G1: 2 309 in the loop, DESIGN.md
+// "Bucket addition: instruction count").
 // ------------------------------------------------------------------------------------
 template <class C, uint32_t ACC_SPLIT>
 __device__ __forceinline__ void accumulate_body(const typename C::Base *__restrict__ bases, const uint32_t *__restrict__ entries,
@@ -965,15 +966,35 @@ __device__ __forceinline__ void accumulate_body(const typename C::Base *__restri
     const uint32_t g = perm[t / ACC_SPLIT], part = t % ACC_SPLIT;
     const uint32_t cnt = hist[g];           // 1 .. heavy_threshold
     const uint32_t *e = entries + offs[g];
+    // One lane per bucket is the wide path only, whose entries never carry the endo bit: no beta multiplication in that loop.
+    constexpr bool ENDO = ACC_SPLIT != 1;
     typename C::Acc acc = C::inf();
     if (part < cnt) {
         uint32_t v = e[part];
         typename C::Base cur = bases[v & 0x3fffffffu];
-        for (uint32_t j = part; j < cnt; j += ACC_SPLIT) {
+        uint32_t j = part;
+        if constexpr (C::HEAD) {
+            // The first two entries as affine + affine.  A list of one entry, or an infinity base among the two, takes
+            // the loop from the start: there an accumulator at infinity is the rare path of the mixed addition.
+            if (j + ACC_SPLIT < cnt) {
+                const uint32_t v1 = e[j + ACC_SPLIT];
+                const typename C::Base b1 = bases[v1 & 0x3fffffffu];
+                if (C::head_ok(cur, b1)) {
+                    uint32_t vn = v1;
+                    typename C::Base nxt = b1;
+                    if (j + 2 * ACC_SPLIT < cnt) { vn = e[j + 2 * ACC_SPLIT]; nxt = bases[vn & 0x3fffffffu]; }
+                    acc = C::template madd_head<ENDO>(cur, (v >> 31) != 0, ((v >> 30) & 1) != 0, b1, (v1 >> 31) != 0, ((v1 >> 30) & 1) != 0);
+                    j += 2 * ACC_SPLIT;
+                    v = vn;
+                    cur = nxt;
+                }
+            }
+        }
+        for (; j < cnt; j += ACC_SPLIT) {
             uint32_t vn = v;
             typename C::Base nxt = cur;
             if (j + ACC_SPLIT < cnt) { vn = e[j + ACC_SPLIT]; nxt = bases[vn & 0x3fffffffu]; }
-            acc = C::madd(acc, cur, (v >> 31) != 0, ((v >> 30) & 1) != 0);
+            acc = C::template madd<ENDO>(acc, cur, (v >> 31) != 0, ((v >> 30) & 1) != 0);
             v = vn;
             cur = nxt;
         }
