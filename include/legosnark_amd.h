@@ -350,6 +350,43 @@ int lsa_fr_hadamard_quotient(const void *a_mont, const void *b_mont, const void 
  * on_device != 0: out is a device pointer and the call is asynchronous on lsa_stream(); else a host pointer, blocking. */
 int lsa_fr_lagrange(size_t big_log, int small_log, const void *omega_mont, const void *t_mont, void *out_mont, int on_device);
 
+/* ---- Fr vectors as row-major matrices: the matrix-product gadget (CPMat / CPmmp, src/examples/matrixsc.cc) ---------- */
+/* Weighted sums of the rows or of the columns of a rows x cols matrix M (row-major, M[r * cols + c]):
+ *   side 0: out[c] = sum_r w[r] * M[r * cols + c]   (cols results; w has rows entries)
+ *           -- the contraction in DPMatrixMle's constructor (src/prototools/mle.h:241-258, v[r] = sum_l A[(l << d) + r] eqTbl[l])
+ *           with M = A, rows = cols = 2^d and w = the table of lsa_fr_eq_table(rho, d, 0);
+ *   side 1: out[r] = sum_c M[r * cols + c] * w[c]   (rows results; w has cols entries).
+ * Any dimensions; a summed dimension of zero gives zeros, no outputs is a successful no-op.  Inputs are libff Montgomery
+ * words; the outputs are canonical (< r), so the bytes are those of the reference's loop whatever the order of summation
+ * (csrc/fr_dot.h: four products per Montgomery reduction on 29-bit limbs).  M is read once; when the outputs alone cannot
+ * fill the device the summed dimension is cut into lsa_fr_matvec_slices(rows, cols, side) slices and a finishing kernel
+ * adds their partial sums (csrc/fr_matrix.hip).
+ * on_device != 0: m, w, out are device pointers (16-byte aligned) and the call is asynchronous on lsa_stream(), with no host
+ * synchronisation inside (the staging -- the limbs of w, the slices' partial sums -- is grow-only and owned by the library:
+ * only the first call of a larger size waits for the device).  Else host pointers and a blocking call.
+ * LSA_ERR_INVALID, before any device work: side not 0 or 1, rows * cols * 32 overflows size_t, a null pointer with a
+ * non-empty extent, out overlapping m or w, a misaligned device pointer. */
+int lsa_fr_matvec(const void *m_mont, size_t rows, size_t cols, const void *w_mont, int side, void *out_mont, int on_device);
+
+/* C (rows_a x cols_b) = A (rows_a x inner) * B (inner x cols_b), all row-major: the witness of the matrix-product gadget
+ * (the triple loop of src/examples/matrixsc.cc:83-91).  Any dimensions; inner == 0 gives zeros, an empty C is a successful
+ * no-op.  Values, modes and refusals as for lsa_fr_matvec (c must not overlap a or b).  A workgroup owns a 32 x 32 tile of C
+ * and stages the tiles of A and B in LDS as limbs, 16 of the summed dimension at a time; edge tiles are predicated, the
+ * caller's buffers are never padded (csrc/fr_matrix.hip). */
+int lsa_fr_matmul(const void *a_mont, const void *b_mont, size_t rows_a, size_t inner, size_t cols_b, void *c_mont, int on_device);
+
+/* Test and tool support, not needed to use the two calls above: their compiled shape, so that tests and benchmarks follow a
+ * retune.  `which` is one of the selectors below (the comment names the value returned); 0 for an unknown selector. */
+#define LSA_FR_PARAM_MATMUL_TILE 0        /* -> edge of a workgroup's tile of C */
+#define LSA_FR_PARAM_MATMUL_KSTEP 1       /* -> elements of the summed dimension staged per step */
+#define LSA_FR_PARAM_DOT_MAX_PARTIALS 2   /* -> reduced partial sums added up before a product brings them back below 2r (csrc/fr_dot.h) */
+#define LSA_FR_PARAM_DOT_GROUP 3          /* -> products per partial sum */
+#define LSA_FR_PARAM_MATVEC_SMALL 4       /* -> lsa_fr_matvec: a matrix of at most this many elements is one workgroup's */
+size_t lsa_fr_matrix_param(int which);
+/* (Test and tool support.)  Slices of the summed dimension lsa_fr_matvec cuts a rows x cols matrix into: 1 = the kernel writes out itself, more =
+ * partial sums and the finishing kernel.  0 for arguments the call refuses. */
+size_t lsa_fr_matvec_slices(size_t rows, size_t cols, int side);
+
 /* ---- pairing ---------------------------------------------------------------------------- */
 /* out[i] = miller_loop(precompute_G1(P_i), precompute_G2(Q_i)), i < n: replaces libff
  * alt_bn128_pp::precompute_G1 / precompute_G2 / miller_loop (src/utils/globl.h:96-102,

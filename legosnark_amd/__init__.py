@@ -106,6 +106,12 @@ def lib():
         L.lsa_fr_hadamard_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_lagrange.argtypes = [C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.lsa_fr_matvec.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.lsa_fr_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]
+        L.lsa_fr_matrix_param.argtypes = [C.c_int]
+        L.lsa_fr_matrix_param.restype = C.c_size_t
+        L.lsa_fr_matvec_slices.argtypes = [C.c_size_t, C.c_size_t, C.c_int]
+        L.lsa_fr_matvec_slices.restype = C.c_size_t
         L.lsa_fr_sumcheck_round.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_scale_upper.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_eq_table.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int]
@@ -714,6 +720,79 @@ def fr_lagrange(big_log, small_log, omega, t, out=None):
     _after_torch(out)
     _check(lib().lsa_fr_lagrange(big_log, sl, _host_ptr(omega), _host_ptr(t), _ptr(out), 1))
     return out
+
+
+def fr_matrix_params():
+    """The compiled shape of fr_matmul / fr_matvec (lsa_fr_matrix_param): the edge of a workgroup's tile of C, the K-step, the
+    partial sums csrc/fr_dot.h adds up before it brings the running sum back below 2r, the products per partial sum, and
+    the element count up to which fr_matvec is one workgroup's."""
+    names = ("matmul_tile", "matmul_kstep", "dot_max_partials", "dot_group", "matvec_small")
+    return {name: int(lib().lsa_fr_matrix_param(i)) for i, name in enumerate(names)}
+
+
+def fr_matvec_slices(rows, cols, side=0):
+    """Slices of the summed dimension fr_matvec cuts a rows x cols matrix into (1: no finishing kernel)."""
+    return int(lib().lsa_fr_matvec_slices(rows, cols, side))
+
+
+def _fr_matrix_operand(name, x, entries, what):
+    """One operand after its length check: the host array as contiguous (n, 4) uint64, or the device tensor as given."""
+    if isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4)
+        n = len(x)
+    else:
+        n = _fr_vec_len(x)
+    if n != entries:
+        raise ValueError("%s: %s has %d entries, the dimensions say %d" % (name, what, n, entries))
+    return x
+
+
+def _fr_matrix_call(name, ins, nout, out, call):
+    host = isinstance(ins[0], np.ndarray)
+    if any(isinstance(x, np.ndarray) != host for x in ins):
+        raise ValueError("%s: operands must be all numpy arrays or all torch CUDA tensors" % name)
+    if host:
+        if out is not None:
+            raise ValueError("%s: out is for torch CUDA tensors (numpy in gives a new numpy array)" % name)
+        res = np.zeros((nout, 4), dtype=np.uint64)
+        call([_host_ptr(x) for x in ins], _host_ptr(res), 0)
+        return res
+    if out is None:
+        import torch
+        out = torch.empty((nout, 4), dtype=torch.int64, device=ins[0].device)
+    elif _fr_vec_len(out) != nout:
+        raise ValueError("%s: out has %d entries, the dimensions say %d" % (name, _fr_vec_len(out), nout))
+    _after_torch(*ins, out)
+    call([_ptr(x) for x in ins], _ptr(out), 1)
+    return out
+
+
+def fr_matvec(m, w, rows, cols, side=0, out=None):
+    """Weighted sums over a row-major rows x cols matrix of Fr.  side 0: out[c] = sum_r w[r] m[r][c] (w: rows entries, cols
+    results) -- DPMatrixMle's contraction (mle.h:241-258) with w = fr_eq_table(rho, 0); side 1: out[r] = sum_c m[r][c] w[c]
+    (w: cols entries, rows results).  numpy in -> a new numpy array; torch CUDA tensors in -> a torch CUDA tensor (`out`, or a
+    new one), asynchronous on the library's stream."""
+    rows, cols, side = int(rows), int(cols), int(side)
+    if rows < 0 or cols < 0:
+        raise ValueError("fr_matvec: negative dimension")
+    if side not in (0, 1):
+        raise ValueError("fr_matvec: side %r (0: sums of rows weighted by w[r], 1: sums of columns weighted by w[c])" % side)
+    m = _fr_matrix_operand("fr_matvec", m, rows * cols, "m")
+    w = _fr_matrix_operand("fr_matvec", w, cols if side else rows, "w")
+    return _fr_matrix_call("fr_matvec", [m, w], rows if side else cols, out,
+                           lambda p, o, dev: _check(lib().lsa_fr_matvec(p[0], rows, cols, p[1], side, o, dev)))
+
+
+def fr_matmul(a, b, rows_a, inner, cols_b, out=None):
+    """C (rows_a x cols_b) = A (rows_a x inner) B (inner x cols_b) over Fr, all row-major (matrixsc.cc:83-91).  numpy in -> a
+    new numpy array; torch CUDA tensors in -> a torch CUDA tensor (`out`, or a new one), asynchronous on the library's stream."""
+    rows_a, inner, cols_b = int(rows_a), int(inner), int(cols_b)
+    if rows_a < 0 or inner < 0 or cols_b < 0:
+        raise ValueError("fr_matmul: negative dimension")
+    a = _fr_matrix_operand("fr_matmul", a, rows_a * inner, "a")
+    b = _fr_matrix_operand("fr_matmul", b, inner * cols_b, "b")
+    return _fr_matrix_call("fr_matmul", [a, b], rows_a * cols_b, out,
+                           lambda p, o, dev: _check(lib().lsa_fr_matmul(p[0], p[1], rows_a, inner, cols_b, o, dev)))
 
 
 def sum_async(group, d_pts, n, d_out):

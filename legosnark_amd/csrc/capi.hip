@@ -730,6 +730,7 @@ static void release_stage_buffers() {
     fr_vec_release();                                // the cached hipGraphs of the Fr recursions (fr_vec.hip)
     pairing_release();
     fr_poly_release();
+    fr_matrix_release();
 }
 
 // ---------------------------------------------------------------- CRS cache behind lsa_g1_msm / lsa_g2_msm
