@@ -5,13 +5,14 @@
 #include <stddef.h>
 #include "../../include/legosnark_amd.h"
 #include "ec.h"
+#include "msm_plan.h"
 
 namespace lsa {
 
 // printf-style error text retrievable through lsa_last_error()
 void set_error(const char *fmt, ...);
 
-unsigned msm_window_bits(size_t n);
+// (msm_window_bits: msm_plan.h)
 
 // Jacobian (libff layout, device) -> affine (device), batch inversion per lane.
 template <class F>

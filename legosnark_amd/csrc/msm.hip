@@ -48,19 +48,7 @@
 
 namespace lsa {
 
-// ------------------------------------------------------------------------------------
-// window choice
-// ------------------------------------------------------------------------------------
-unsigned msm_window_bits(size_t n) {
-    unsigned lg = 0;
-    while ((size_t(1) << (lg + 1)) <= n) lg++;   // floor(log2 n), 0 for n <= 1
-    int c = (int)lg - 4;
-    if (c < 8) c = 8;        // few, wide windows keep the latency-bound fold short for tiny inputs
-    if (c > 16) c = 16;
-    return (unsigned)c;
-}
-
-static inline unsigned num_windows(unsigned c) { return (255 + c - 1) / c; }
+// (window choice, tile sizes, SegList, CoarseMap and every other size the host derives: msm_plan.h)
 
 // ------------------------------------------------------------------------------------
 // kernel 0: Jacobian (libff layout) -> affine, per-lane Montgomery batch inversion
@@ -218,7 +206,6 @@ __global__ __launch_bounds__(256) void k_prepare_g2(const Jac<Fq2> *__restrict__
 //   1c k_tile_scan  per (window, bucket): exclusive prefix over the tiles (u32) and the
 //                   bucket population hist[k][b].
 // ------------------------------------------------------------------------------------
-#define SORT_TILE 32768u
 __device__ __forceinline__ void write_digits(const uint32_t *s, int nlimbs, bool negate, size_t col, size_t nv, unsigned c,
                                              unsigned nwin, int32_t *__restrict__ digits) {
     const uint32_t B = 1u << (c - 1);
@@ -300,7 +287,6 @@ __global__ __launch_bounds__(256) void k_tile_scan(const uint16_t *__restrict__ 
 //   b) one block scans the <= 1024 block sums
 //   c) per-block exclusive scan seeded with the block offset
 // ------------------------------------------------------------------------------------
-#define SCAN_PER_BLOCK 2048
 __device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t *lds, uint32_t *total) {
     // 256 lanes; wave-level shuffles then 4 wave totals through LDS
     const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -452,31 +438,14 @@ __global__ __launch_bounds__(1024) void k_tile_scan_rows(const uint16_t *__restr
 // Wide-window path (resident bases with pre-shifted copies, see "Wide windows" below).
 // Every entry is (bin, point reference): bin = segment * B + bucket.  With B = 2^(c-1) up to 2^21
 // the bin space can be too large for an LDS histogram; then the sort runs in two passes:
-// (A) k_rank / k_tile_scan_rows / k_scatter_wide<true> partition all entries by the COARSE bin
-// (bin >> 7; a tile's histogram fits LDS) into 64-bit records (fine bits | entry); (B)
-// k_fine_sort, one workgroup per coarse bin, counts its 128 fine bins in LDS and places the
+// (A) k_hist_wide / k_tile_scan_rows / k_scatter_wide<1|2> partition all entries by the COARSE bin
+// (bin >> 7, or bin >> 6 with 32-bit records; a tile's histogram fits LDS) into 64-bit records
+// (fine bits | entry) or 32-bit ones (sign | fine bits | point reference); (B)
+// k_fine_sort, one workgroup per coarse bin, counts its 128 (64) fine bins in LDS and places the
 // 32-bit entries, writing the per-bin populations and offsets.  With at most 32768 bins (the
-// narrow digits used for small inputs and for segmented calls) pass A alone sorts completely.
+// narrow digits used for small inputs and for segmented calls) pass A alone (k_scatter_wide<0>)
+// sorts completely.  (SegList, the tile sizes of these passes: msm_plan.h.)
 // ------------------------------------------------------------------------------------
-#define WIDE_FINE_BITS 7u
-#define MSM_MAX_SEGMENTS 64u
-// scalar slices of a segmented call: segment j = scalars[off[j] .. off[j+1]) against bases[0 .. len_j)
-struct SegList {
-    uint32_t nseg;
-    uint32_t off[MSM_MAX_SEGMENTS + 1];
-};
-
-// Scalars per workgroup of the wide path's ranking / scatter passes: a tile's entries (nwin per
-// scalar) must fit the u16 counters even when every one of them lands in the same bin
-// (all scalars equal, all their digits equal): 13 x 4096 or 26 x 2048 = 53248 < 65536.
-// Small inputs get 256- or 1024-scalar tiles: a lone workgroup ranking
-// 26 digits of 1024 scalars keeps ONE CU's LDS busy for 13 + 17 us (hist + scatter); with more
-// tiles the LDS atomics of a call spread over several CUs.
-static inline uint32_t wide_tile(uint32_t nwin, size_t n) {
-    if (n <= 4096) return 256u;
-    if (n <= 16384) return 1024u;
-    return nwin > 15 ? 2048u : 4096u;
-}
 __device__ __forceinline__ uint32_t segment_of(const SegList &segs, uint32_t i) {
     uint32_t seg = 0;
     for (uint32_t j = 1; j < segs.nseg; j++) if (i >= segs.off[j]) seg = j;
@@ -492,20 +461,6 @@ __device__ __forceinline__ uint32_t xcd_tile(uint32_t bid, uint32_t ntiles) {
     const uint32_t q = ntiles >> 3, r = ntiles & 7u, x = bid & 7u, j = bid >> 3;
     return x * q + (x < r ? x : r) + j;
 }
-
-// Bucket -> coarse bin of the first sort pass.  Windows of the widest width c reach all 2^(c-1)
-// buckets, windows one bit narrower (5 of the 13 at n = 2^20) only the lower half, so a bucket of
-// the lower half holds more than twice as many entries as one of the upper half (36 against 16):
-// bins of equal POPULATION take 2^sh_lo buckets below `half` and 2^sh_hi above.  half = 0 makes it a
-// plain shift by sh_hi.
-struct CoarseMap {
-    uint32_t half, sh_lo, sh_hi, nlo;      // nlo = half >> sh_lo bins below `half`
-    __device__ __forceinline__ uint32_t bin(uint32_t b) const { return b < half ? b >> sh_lo : nlo + ((b - half) >> sh_hi); }
-    __device__ __forceinline__ uint32_t fine(uint32_t b) const { return b < half ? b & ((1u << sh_lo) - 1) : (b - half) & ((1u << sh_hi) - 1); }
-    // bin -> its first bucket and its bucket count
-    __device__ __forceinline__ uint32_t first(uint32_t bin_) const { return bin_ < nlo ? bin_ << sh_lo : half + ((bin_ - nlo) << sh_hi); }
-    __device__ __forceinline__ uint32_t bits(uint32_t bin_) const { return bin_ < nlo ? sh_lo : sh_hi; }
-};
 
 // One workgroup per tile of WIDE_TILE scalars, ALL windows: the histogram of the (coarse) bins of
 // the tile's entries in LDS (u16 pairs, one ds_add_u32 per entry) -> the tile's row of tile_hist.
@@ -601,7 +556,7 @@ __global__ __launch_bounds__(1024) void k_scatter_wide(const Fr *__restrict__ sc
 // Partitioned two-pass sort (the large single-MSM shape: 2^19 .. 2^21 buckets).  The scatter of
 // k_scatter_wide writes 13.6 M four-byte records at n = 2^20 in runs of ~6 (one run per tile and
 // coarse bin, 8192 bins): 183 us, against 35 us for the same tiles without the stores
-// (k_hist_wide).  Here the first pass cuts the bin space into only PART_SEGS = 256 segments and
+// (k_hist_wide).  Here the first pass cuts the bin space into at most PART_SEGS = 768 segments and
 // stages a tile's records in LDS, so a tile leaves ~100-record runs behind (whole cache lines),
 // and the second pass -- one workgroup per segment, 2^11 .. 2^13 fine buckets counted in LDS -- does
 // its scattered stores inside the segment's own few hundred KB, which stay in one L2.
@@ -624,9 +579,6 @@ __device__ __forceinline__ uint32_t lds_inc_rank(uint32_t *counters, uint32_t id
     }
     return atomicAdd(&counters[idx], 1u);
 }
-#define PART_TILE 2048u
-#define PART_SEGS 768u       // at most: 512 bins of 2^9 buckets below B/2 and 256 of 2^10 above, at 2^19 buckets
-#define PART_STAGE 28672u     // records the second pass can stage in LDS (a segment holds 26624 +- 160 at n = 2^20)
 __global__ __launch_bounds__(1024) void k_partition(const Fr *__restrict__ scalars, size_t n, SegList segs, WidePlan pl, uint32_t B, uint32_t Bc,
                                                     CoarseMap cm, uint32_t pitch, const uint16_t *__restrict__ tile_hist,
                                                     const uint32_t *__restrict__ hist_c, uint32_t *__restrict__ offs_c,
@@ -856,7 +808,6 @@ __global__ __launch_bounds__(1024) void k_fine_sort(const Rec *__restrict__ recs
 // ------------------------------------------------------------------------------------
 // lanes per bucket in k_accumulate: 2 on the plain path (GLV halves the bucket count; two lanes keep
 // >= 2.5 wavefronts per SIMD slot in flight), 1 on the wide path (2^19 .. 2^21 buckets)
-#define SIZE_BINS 1025          // bin 0 unused (total), bins 1..1024
 // population -> bin: ((cnt - 1) >> bin_shift) + 1 in [1, SIZE_BINS - 1] for cnt in [1, thr]
 __device__ __forceinline__ uint32_t size_bin(uint32_t cnt, uint32_t bin_shift) { return ((cnt - 1) >> bin_shift) + 1; }
 template <class C>
@@ -1086,7 +1037,6 @@ __device__ __forceinline__ typename C::Acc wave_sum(typename C::Acc v, unsigned 
 // chunk one wavefront (8 sequential mixed adds per lane, then a shuffle tree);
 // k_heavy_finish sums a bucket's chunk partials.  With uniformly random scalars and c | 128
 // there are no heavy buckets and all three exit at once.
-#define HEAVY_CHUNK 512u
 // Chunk size of this call: 512 entries, doubled (up to 4096) while that still leaves >= 2048 chunks.
 // A chunk costs 6 general additions per lane (the shuffle tree) on top of its mixed additions --
 // 8 per lane at 512 entries, i.e. 40 % overhead, which is right for a handful of heavy buckets
@@ -1642,8 +1592,6 @@ int msm_profile_last(float ms[LSA_MSM_STAGES]) {
     return cnt;
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 static int tail_slots_ready() {
     if (g_overlap < 0) g_overlap = getenv("LSA_NO_OVERLAP") ? 0 : 1;
     if (!g_tail[0].done) {
@@ -1660,15 +1608,15 @@ static int tail_slots_ready() {
 
 static int msm_func_attrs() {
     static bool lds_attr_set = false;
-    if (!lds_attr_set) {   // > 64 KiB of dynamic LDS needs an explicit opt-in
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_wide<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_wide<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_wide<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rank), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_hist_wide), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_partition), hipFuncAttributeMaxDynamicSharedMemorySize, 13 * PART_TILE * 4));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fine_sort_part), hipFuncAttributeMaxDynamicSharedMemorySize, 155648));
+    if (!lds_attr_set) {   // > 64 KiB of dynamic LDS needs an explicit opt-in (the limits: msm_plan.h, where plan_pipeline's requests are checked against them)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BIN_WORDS));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_wide<0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BIN_WORDS));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_wide<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BIN_WORDS));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_wide<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BIN_WORDS));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rank), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BIN_HALVES));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_hist_wide), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BIN_HALVES));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_partition), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_PARTITION));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fine_sort_part), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_FINE_SORT_PART));
         lds_attr_set = true;
     }
     return LSA_OK;
@@ -1707,15 +1655,29 @@ int msm_warmup(hipStream_t st) {
     return LSA_OK;
 }
 
-// ---- the slot interface other pipelines (msm_compact.hip) run their tails through
+// ---- the tail slots: one copy of the bookkeeping for both pipelines (msm_pipeline below, msm_compact.hip through msm.h)
+static int grow_tail_slot(TailBuf &t, size_t bytes) {
+    if (bytes <= t.ws.cap) return LSA_OK;
+    if (t.pending) HIPCHK(hipEventSynchronize(t.done));            // about to reallocate: the old tail must be finished
+    if (t.ws.ensure(bytes) != 0) { set_error("msm: tail workspace allocation of %zu bytes failed", bytes); return LSA_ERR_NOMEM; }
+    return LSA_OK;
+}
+// msm_slot_begin grows only the slot it hands out: a prover that only ever blocks keeps re-using one slot and grows one slot
+// per problem size (when all eight grew together, the first G2 MSM of a process -- the reference's provers issue a handful,
+// each blocking -- paid nine hipFree + hipMalloc pairs, 4 ms on a good box and tens of ms on a slow one).
+// A QUEUED large call (the integrator's pipelined form) grows every slot at once before it takes its own: its successors
+// take the other slots within microseconds, and a new problem size then pays its allocations in one call instead of in eight.
+static int grow_all_tail_slots(size_t bytes) {
+    int rc = tail_slots_ready();
+    for (auto &t : g_tail) if (!rc) rc = grow_tail_slot(t, bytes);
+    return rc;
+}
 int msm_slot_begin(hipStream_t st, size_t ws_bytes, const void *d_out, MsmSlot *slot, bool inline_tail) {
     int rc = tail_slots_ready();
     if (rc) return rc;
     TailBuf &tb = g_tail[g_slot];
-    if (ws_bytes > tb.ws.cap) {
-        if (tb.pending) HIPCHK(hipEventSynchronize(tb.done));          // about to reallocate: the old tail must be finished
-        if (tb.ws.ensure(ws_bytes) != 0) { set_error("msm: tail workspace allocation of %zu bytes failed", ws_bytes); return LSA_ERR_NOMEM; }
-    }
+    rc = grow_tail_slot(tb, ws_bytes);
+    if (rc) return rc;
     if (tb.pending) HIPCHK(hipStreamWaitEvent(st, tb.done, 0));        // the front may not overwrite what the slot's last tail still reads
     slot->tail = (g_overlap && !inline_tail) ? tb.stream : st;
     slot->ws = tb.ws.ptr;
@@ -1724,29 +1686,52 @@ int msm_slot_begin(hipStream_t st, size_t ws_bytes, const void *d_out, MsmSlot *
     tb.out = d_out;
     return LSA_OK;
 }
-int msm_slot_handover(MsmSlot *slot, hipStream_t st) {
-    TailBuf &tb = g_tail[slot->index];
-    if (slot->tail != st) {
-        HIPCHK(hipEventRecord(tb.front_done, st));
-        HIPCHK(hipStreamWaitEvent(slot->tail, tb.front_done, 0));
-    }
-    // results appear in call order wherever two calls write the same place: behind every earlier tail with this destination
-    for (int i = 0; i < NTAIL; i++) {
-        TailBuf &o = g_tail[i];
-        if (i == slot->index || !o.pending || o.out != tb.out) continue;
+// the front (on st) is issued: the slot's stream continues from here
+static int slot_front_to_tail(TailBuf &tb, hipStream_t tail, hipStream_t st) {
+    if (tail == st) return LSA_OK;
+    HIPCHK(hipEventRecord(tb.front_done, st));
+    HIPCHK(hipStreamWaitEvent(tail, tb.front_done, 0));
+    return LSA_OK;
+}
+// Results appear in call order wherever two calls write the same place.  The two pipelines order their tails differently,
+// and on purpose:
+//   compact: its tail writes d_out itself, so the whole tail waits -- at hand-over -- for every earlier tail with this
+//            destination, and for nothing else; a tail that finished long ago costs no wait command.
+//   large:   its tail computes into the slot and only k_publish touches d_out, so the waits sit right before k_publish, behind
+//            the reduction kernels already enqueued (at hand-over they would serialise the reduction behind the previous
+//            tail).  It waits for the previous slot's tail whatever its destination -- results of queued large calls appear
+//            in call order -- and for every other pending tail with this destination (the compact pipeline's among them).
+static int publish_order_compact(TailBuf &tb, hipStream_t tail) {
+    for (auto &o : g_tail) {
+        if (&o == &tb || !o.pending || o.out != tb.out) continue;
         // (a tail that finished long ago needs no wait command: a blocking small call otherwise issues up to seven of them)
         if (!o.unjoined && hipEventQuery(o.done) == hipSuccess) { o.pending = false; continue; }
-        HIPCHK(hipStreamWaitEvent(slot->tail, o.done, 0));
+        HIPCHK(hipStreamWaitEvent(tail, o.done, 0));
     }
     return LSA_OK;
 }
-int msm_slot_end(MsmSlot *slot, hipStream_t st) {
-    TailBuf &tb = g_tail[slot->index];
-    HIPCHK(hipEventRecord(tb.done, slot->tail));
-    tb.pending = true;
-    tb.unjoined = slot->tail != st;
-    if (slot->tail != st || g_overlap == false) g_slot = (g_slot + 1) % tail_slots();      // (an inline tail = a blocking call: the slot is free again when it returns)
+static int publish_order_large(TailBuf &tb, TailBuf &prev, hipStream_t tail) {
+    if (prev.pending && &prev != &tb) HIPCHK(hipStreamWaitEvent(tail, prev.done, 0));
+    for (auto &o : g_tail)
+        if (&o != &tb && &o != &prev && o.pending && o.out == tb.out) HIPCHK(hipStreamWaitEvent(tail, o.done, 0));
     return LSA_OK;
+}
+int msm_slot_handover(MsmSlot *slot, hipStream_t st) {
+    TailBuf &tb = g_tail[slot->index];
+    int rc = slot_front_to_tail(tb, slot->tail, st);
+    return rc ? rc : publish_order_compact(tb, slot->tail);
+}
+// the tail is issued; `advance`: the next call takes the next slot
+static int slot_finish(TailBuf &tb, hipStream_t tail, hipStream_t st, bool advance) {
+    HIPCHK(hipEventRecord(tb.done, tail));
+    tb.pending = true;
+    tb.unjoined = tail != st;
+    if (advance) g_slot = (g_slot + 1) % tail_slots();
+    return LSA_OK;
+}
+int msm_slot_end(MsmSlot *slot, hipStream_t st) {
+    // (an inline tail = a blocking call: the slot is free again when it returns)
+    return slot_finish(g_tail[slot->index], slot->tail, st, slot->tail != st || g_overlap == false);
 }
 
 size_t msm_base_bytes(int group) { return group == 1 ? sizeof(CurveG1::Base) : sizeof(CurveG2::Base); }
@@ -1826,13 +1811,22 @@ template int normalize_to_affine<Fq2>(const Jac<Fq2> *, Aff<Fq2> *, size_t, hipS
 // Price: 26 (24) x the base memory (G1 64 B, G2 128 B per point and copy) and one pass of 255
 // doublings + 25 batch normalisations per key.
 // ------------------------------------------------------------------------------------
-static unsigned table_copies(size_t n_table) { return table_grid(n_table).ncopies; }
-static size_t wide_big_min() {
-    static const size_t v = getenv("LSA_WIDE_BIG_MIN") ? (size_t)atoll(getenv("LSA_WIDE_BIG_MIN")) : (size_t)1 << 16;
-    return v;
-}
-static WidePlan wide_plan(size_t n_table, size_t n_call, unsigned nseg) {
-    return wide_plan_for(n_table, nseg == 1 && n_call >= wide_big_min());
+// The switches of the plan (msm_plan.h: MsmSwitches), read from the environment once per process.
+static MsmSwitches &switches() {
+    static MsmSwitches sw = [] {
+        const auto is_one = [](const char *name) { const char *e = getenv(name); return e && e[0] == '1'; };
+        MsmSwitches v;
+        v.no_rec32 = getenv("LSA_NO_REC32") != nullptr;
+        v.no_part = getenv("LSA_NO_PART") != nullptr;
+        if (const char *e = getenv("LSA_WIDE_SPLIT")) v.wide_split = (uint32_t)atoi(e);
+        v.g2_pair = is_one("LSA_G2_PAIR");
+        v.no_reduce_bits = getenv("LSA_NO_REDUCE_BITS") != nullptr;
+        v.no_lane_l1 = getenv("LSA_NO_LANE_L1") != nullptr;
+        v.g2_lane_l1 = is_one("LSA_G2_LANE_L1");
+        if (const char *e = getenv("LSA_WIDE_BIG_MIN")) v.wide_big_min = (size_t)atoll(e);
+        return v;
+    }();
+    return sw;
 }
 unsigned msm_table_windows(int /*group*/, size_t n) { return table_copies(n); }
 
@@ -1840,7 +1834,11 @@ static size_t g_merge_min = 0;
 static bool g_merge_min_explicit = false;
 // n != 0: vectors of at least n points get the copies and MSMs of at least n pairs use them;
 // 0: defaults (copies from LSA_PRECOMPUTE_MIN / 2^19 points on, used by MSMs of every size)
-void msm_set_merge_min(size_t n) { g_merge_min = n; g_merge_min_explicit = n != 0; }
+void msm_set_merge_min(size_t n) {
+    g_merge_min = n;
+    g_merge_min_explicit = n != 0;
+    switches().table_use_min = n ? n : 1;
+}
 size_t msm_merge_min() {
     if (g_merge_min == 0) {
         const char *e = getenv("LSA_PRECOMPUTE_MIN");
@@ -1849,9 +1847,8 @@ size_t msm_merge_min() {
     return g_merge_min;
 }
 bool msm_merge_min_is_explicit() { return g_merge_min_explicit; }
-static size_t table_use_min() { return g_merge_min_explicit ? msm_merge_min() : 1; }
 // whether an MSM of n pairs on a handle that carries the copies runs over them (the wide-window pipeline)
-bool msm_uses_table(size_t n) { return n >= table_use_min(); }
+bool msm_uses_table(size_t n) { return n >= switches().table_use_min; }
 
 template <class C>
 __global__ __launch_bounds__(256) void k_shift_window(const typename C::Base *__restrict__ prev, Jac<typename C::Field> *__restrict__ out,
@@ -1901,8 +1898,208 @@ template int precompute_windows<Fq2>(void *, size_t, hipStream_t);
 
 // field multiplications per point-scalar pair in the accumulate kernel (bench.py's VALU roofline)
 unsigned msm_field_mults_per_pair(size_t n, size_t table_n) {
-    if (table_n && n >= table_use_min()) return wide_plan(table_n, n, 1).nwin * 10;   // mixed XYZZ addition: 8M + 2S
+    if (table_n && n >= switches().table_use_min) return wide_plan(table_n, n, 1, switches()).nwin * 10;   // mixed XYZZ addition: 8M + 2S
     return 16 * 10 + 8;                                                                // 16 additions + 8 beta-multiplications (GLV)
+}
+
+// ------------------------------------------------------------------------------------
+// The general pipeline.  plan_pipeline (msm_plan.h) decides everything a call's shape decides; msm_pipeline
+// gets the workspaces and the slot, binds the pointers and issues the three stages below.
+// ------------------------------------------------------------------------------------
+// The buffers of one call, bound in one place from the plan's two layouts.
+template <class A>
+struct MsmBuffers {
+    // front workspace (g_ws): sort and accumulate, reused by every call, ordered on the caller's stream
+    uint32_t *hist, *heavy_count, *offs, *bsum, *bin_count, *bin_start, *bin_cursor, *perm;
+    int32_t *digits;
+    uint16_t *rank, *tile_hist;
+    uint32_t *tile_base, *entries, *heavy_list, *chunk_off;
+    A *hpart;
+    void *recs;                      // coarse-sorted records, u32 or u64
+    uint32_t *hist_c, *offs_c;       // populations and offsets of the first pass's bins
+    // the slot's workspace: what the tail reads
+    A *buckets, *wave_out, *window_sums;
+    void *res;                       // Jac[nseg]
+
+    MsmBuffers(const PipelinePlan &p, void *front_ws, void *tail_ws) {
+        char *ws = (char *)front_ws, *tws = (char *)tail_ws;
+        hist = (uint32_t *)(ws + p.front[F_HIST]);
+        heavy_count = hist + p.nb;
+        offs = (uint32_t *)(ws + p.front[F_OFFS]);
+        bsum = (uint32_t *)(ws + p.front[F_BSUM]);
+        bin_count = (uint32_t *)(ws + p.front[F_BINS]);
+        bin_start = bin_count + SIZE_BINS;
+        bin_cursor = bin_start + SIZE_BINS;
+        perm = (uint32_t *)(ws + p.front[F_PERM]);
+        digits = (int32_t *)(ws + p.front[F_DIGITS]);
+        rank = (uint16_t *)(ws + p.front[F_RANK]);
+        tile_hist = (uint16_t *)(ws + p.front[F_THIST]);
+        tile_base = (uint32_t *)(ws + p.front[F_TBASE]);
+        entries = (uint32_t *)(ws + p.front[F_ENTRIES]);
+        heavy_list = (uint32_t *)(ws + p.front[F_HEAVY]);
+        chunk_off = (uint32_t *)(ws + p.front[F_CHOFF]);
+        hpart = (A *)(ws + p.front[F_HPART]);
+        recs = ws + p.front[F_RECS];
+        hist_c = p.fine ? (uint32_t *)(ws + p.front[F_CHIST]) : hist;       // one pass: the bins ARE the buckets
+        offs_c = p.fine ? (uint32_t *)(ws + p.front[F_COFFS]) : offs;
+        buckets = (A *)(tws + p.tail[T_BUCKETS]);
+        wave_out = (A *)(tws + p.tail[T_WAVE]);
+        window_sums = (A *)(tws + p.tail[T_WIN]);
+        res = tws + p.tail[T_RES];
+    }
+};
+
+// The call's row of profiling events (EV_MARKS of them), null when profiling is off.
+struct Marks {
+    hipEvent_t *ev;
+    void operator()(int i, hipStream_t s) const { if (ev) (void)hipEventRecord(ev[i], s); }
+};
+
+// ---- sort stage (marks 1..3): entries ordered by bucket, populations in hist, offsets in offs
+template <class C>
+static void launch_sort(const PipelinePlan &p, const MsmBuffers<typename C::Acc> &b, const Fr *d_scalars, const SegList &segs, hipStream_t st,
+                        const Marks &mark) {
+    const size_t n = p.n;
+    if (p.wide) {
+        hipLaunchKernelGGL(k_hist_wide, dim3(p.wtiles), dim3(1024), p.lds_hist_wide, st, d_scalars, n, segs, p.pl, p.B, p.Bc, p.cm, p.pitch, p.wtile, b.tile_hist);
+        mark(1, st);
+        // (also clears heavy_count and the three bin arrays for launch_accumulate)
+        hipLaunchKernelGGL(k_tile_scan_rows, dim3((p.Bc + 31) / 32), dim3(1024), 0, st, b.tile_hist, p.Bc, p.wtiles, p.pitch, b.tile_base, b.hist_c, b.heavy_count,
+                           b.bin_count, (uint32_t)(3 * SIZE_BINS));
+        mark(2, st);
+        if (p.part) {
+            hipLaunchKernelGGL(k_partition, dim3(p.wtiles), dim3(1024), p.lds_partition, st, d_scalars, n, segs, p.pl, p.B, p.Bc, p.cm, p.pitch,
+                               b.tile_hist, b.hist_c, b.offs_c, b.tile_base, (uint32_t *)b.recs);
+            hipLaunchKernelGGL(k_fine_sort_part, dim3(p.Bc), dim3(1024), p.lds_fine_sort_part, st, (const uint32_t *)b.recs, b.offs_c, b.hist_c,
+                               b.tile_base, p.pitch, p.wtiles, p.cm, segs, p.win_stride, p.stage_cap, b.entries, b.hist, b.offs);
+        } else if (p.rec32) {
+            hipLaunchKernelGGL(k_scatter_wide<2>, dim3(p.wtiles), dim3(1024), p.lds_scatter_wide, st, d_scalars, n, segs, p.pl, p.B, p.Bc, p.pitch, p.wtile, b.hist_c, b.offs_c, b.tile_base, b.recs, p.win_stride);
+            hipLaunchKernelGGL(k_fine_sort<uint32_t>, dim3(p.Bc), dim3(1024), 0, st, (const uint32_t *)b.recs, b.offs_c, b.hist_c, b.entries, b.hist, b.offs);
+        } else if (p.fine) {
+            hipLaunchKernelGGL(k_scatter_wide<1>, dim3(p.wtiles), dim3(1024), p.lds_scatter_wide, st, d_scalars, n, segs, p.pl, p.B, p.Bc, p.pitch, p.wtile, b.hist_c, b.offs_c, b.tile_base, b.recs, p.win_stride);
+            hipLaunchKernelGGL(k_fine_sort<uint64_t>, dim3(p.Bc), dim3(1024), 0, st, (const uint64_t *)b.recs, b.offs_c, b.hist_c, b.entries, b.hist, b.offs);
+        } else {
+            hipLaunchKernelGGL(k_scatter_wide<0>, dim3(p.wtiles), dim3(1024), p.lds_scatter_wide, st, d_scalars, n, segs, p.pl, p.B, p.Bc, p.pitch, p.wtile, b.hist_c, b.offs_c, b.tile_base, (void *)b.entries, p.win_stride);
+        }
+        mark(3, st);
+    } else {
+        hipLaunchKernelGGL((k_digits<C::GLV>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, n, p.c, p.nwin, b.digits);
+        hipLaunchKernelGGL(k_rank, dim3(p.ntiles, p.nwin), dim3(1024), p.lds_rank, st, b.digits, p.nv, p.B, p.ntiles, b.rank, b.tile_hist, 0u);
+        hipLaunchKernelGGL(k_tile_scan, dim3((p.nb + 255) / 256), dim3(256), 0, st, b.tile_hist, p.B, p.ntiles, p.nb, b.tile_base, b.hist);
+        mark(1, st);
+        hipLaunchKernelGGL(k_scan_sums, dim3(p.scan_blocks), dim3(256), 0, st, b.hist, p.nb, b.bsum);
+        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, st, b.bsum, p.scan_blocks);
+        hipLaunchKernelGGL(k_scan_final, dim3(p.scan_blocks), dim3(256), 0, st, b.hist, b.bsum, p.nb, b.offs);
+        mark(2, st);
+        hipLaunchKernelGGL(k_scatter, dim3(p.ntiles, p.nwin), dim3(1024), p.lds_scatter, st, b.digits, b.rank, b.offs, b.tile_base, p.nv, n, p.B, p.ntiles, b.entries, 0u);
+        mark(3, st);
+    }
+}
+
+// ---- accumulate stage (marks 4, 5): bucket order, accumulation, heavy buckets
+template <class C>
+static int launch_accumulate(const PipelinePlan &p, const MsmBuffers<typename C::Acc> &b, const typename C::Base *d_bases, hipStream_t st, const Marks &mark) {
+    constexpr bool g2 = std::is_same<C, CurveG2>::value;
+    // the counters of the ordering stage: a wide sort's k_tile_scan_rows has cleared them (two memset launches less);
+    // a shared sort launched nothing
+    if (!p.wide || p.reuse_sort) {
+        HIPCHK(hipMemsetAsync(b.heavy_count, 0, 4, st));
+        HIPCHK(hipMemsetAsync(b.bin_count, 0, (size_t)3 * SIZE_BINS * 4, st));
+    }
+    const unsigned sb = (p.nb + 2047) / 2048;
+    const uint32_t gsz = 0u, ngroups = 1;
+    hipLaunchKernelGGL((k_size_hist<C>), dim3(sb), dim3(256), 0, st, b.hist, p.nb, p.heavy_threshold, b.bin_count, gsz, p.bin_shift);
+    hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(256), 0, st, b.bin_count, b.bin_start, ngroups);
+    hipLaunchKernelGGL((k_size_scatter<C>), dim3(sb), dim3(256), 0, st, b.hist, p.nb, p.heavy_threshold, b.bin_start, b.bin_cursor, b.perm, b.heavy_list, b.heavy_count, b.buckets, gsz, p.bin_shift, p.split);
+    mark(4, st);
+    const dim3 one_lane((p.nb + 255) / 256), two_lanes((p.nb * 2 + 255) / 256);
+    // (measured equal: 3.18 ms for the pair kernel -- 160 VGPRs, no scratch, three wavefronts per SIMD, ~18 % more
+    // instructions per addition -- against 3.09 ms for the one-lane kernel at 2^20 pairs: both are instruction-issue
+    // bound, the 316 B of scratch were never the cost.  LSA_G2_PAIR=1 selects the pair kernel.)
+    if (g2 && p.g2_pair) {
+        if constexpr (g2) hipLaunchKernelGGL(k_accumulate_g2_pair, two_lanes, dim3(256), 0, st, d_bases, b.entries, b.offs, b.hist, b.perm, b.bin_start, b.buckets);
+    } else if (g2 && p.split == 1) {       // (the generic one-lane kernel at full occupancy -- LSA_G2_OCC1 -- lost to this one in rounds 2-4)
+        if constexpr (g2) hipLaunchKernelGGL(k_accumulate_g2_occ2, one_lane, dim3(256), 0, st, d_bases, b.entries, b.offs, b.hist, b.perm, b.bin_start, b.buckets);
+    } else if (p.split == 1) {
+        hipLaunchKernelGGL((k_accumulate<C, 1u>), one_lane, dim3(256), 0, st, d_bases, b.entries, b.offs, b.hist, b.perm, b.bin_start, b.buckets);
+    } else {
+        hipLaunchKernelGGL((k_accumulate<C, 2u>), two_lanes, dim3(256), 0, st, d_bases, b.entries, b.offs, b.hist, b.perm, b.bin_start, b.buckets);
+    }
+    hipLaunchKernelGGL(k_heavy_plan, dim3(1), dim3(256), 0, st, b.hist, b.heavy_list, b.heavy_count, b.chunk_off);
+    hipLaunchKernelGGL((k_accumulate_heavy<C>), dim3(4096), dim3(64), 0, st, d_bases, b.entries, b.offs, b.hist,
+                       b.heavy_list, b.heavy_count, b.chunk_off, b.hpart);
+    hipLaunchKernelGGL((k_heavy_finish<C>), dim3(256), dim3(64), 0, st, b.heavy_list, b.heavy_count, b.chunk_off, b.hpart, b.buckets, p.split);
+    mark(5, st);
+    return LSA_OK;
+}
+
+// ---- tail (marks 6, 7) on the slot's stream: bucket reduction, the point, its publication in d_out
+// lane_l1: the first 16-ary level lane-private (plan.lane_l1_shape and the call sequence, see msm_pipeline)
+template <class C>
+static int launch_tail(const PipelinePlan &p, const MsmBuffers<typename C::Acc> &b, Jac<typename C::Field> *d_out, hipStream_t tail, bool inline_tail,
+                       bool lane_l1, TailBuf &tb, TailBuf &prev, const Marks &mark) {
+    using A = typename C::Acc;
+    using J = Jac<typename C::Field>;
+    constexpr bool g1 = std::is_same<C, CurveG1>::value;
+    if (p.big)
+        hipLaunchKernelGGL((k_reduce1_lane<C>), dim3(p.kw * ((p.T + 63) / 64)), dim3(64), 0, tail, b.buckets, p.B, p.L, p.split, b.wave_out);
+    else
+        hipLaunchKernelGGL((k_reduce1<C>), dim3(p.kw * p.wpw), dim3(64), 0, tail, b.buckets, p.B, p.L, p.logL, p.wpw, p.split, b.wave_out);
+    A *lvl_in = b.wave_out, *lvl_out = b.window_sums;
+    uint32_t m = p.wpw, lm = p.big ? p.logL : p.logL + 4;    // m pairs per window, each covering 2^lm buckets
+    J *res = inline_tail ? d_out : (J *)b.res;
+    const auto level = [&](bool lane) {              // one 16-ary level: m -> ceil(m / 16) pairs per window
+        const uint32_t m_out = (m + 15) / 16;
+        if (lane) hipLaunchKernelGGL((k_reduce2_lane<C>), dim3((m_out + 63) / 64), dim3(64), 0, tail, lvl_in, m, m_out, lm, lvl_out);
+        else hipLaunchKernelGGL((k_reduce2<C>), dim3(p.kw * m_out), dim3(64), 0, tail, lvl_in, m, m_out, lm, lvl_out);
+        std::swap(lvl_in, lvl_out);
+        m = m_out;
+        lm += 4;
+    };
+    level(lane_l1);                                  // at least one level (it leaves the sum in slot 0)
+    if (p.bits_tail) {
+        // one bucket space of 2^19 and more buckets: after the first 16-ary level (m >= 256 left) the rest are bit trees,
+        // which end in the Jacobian point
+        uint32_t nbits = 0;
+        while ((1u << nbits) < m) nbits++;           // indices 0 .. m - 1
+        const uint32_t G = (m + 511) / 512;          // <= 16
+        A *part = lvl_out;                           // (the level just consumed: (nbits + 1) * G + 16 values fit its m_in * 2)
+        A *weighted = part + (size_t)(nbits + 1) * G;
+        hipLaunchKernelGGL((k_reduce_bits_a<C>), dim3(nbits + 1, G), dim3(512), 0, tail, lvl_in, m, nbits, G, part);
+        hipLaunchKernelGGL((k_reduce_bits_b<C>), dim3(nbits + 1), dim3(64), 0, tail, part, nbits, G, lm, weighted);
+        mark(6, tail);
+        hipLaunchKernelGGL((k_reduce_bits_c<C>), dim3(1), dim3(64), 0, tail, weighted, nbits + 1, res);
+    } else {
+        while (m > 1) level(false);
+        mark(6, tail);
+        // lvl_in[2*k] = sum of window k (pairs of (ACC,RUN): stride 2)
+        if (p.wide && p.nseg > 1) {   // every segment's bucket space is a finished sum: convert
+            if constexpr (g1) hipLaunchKernelGGL(k_emit_g1, dim3(p.nseg), dim3(64), 0, tail, lvl_in, res);
+            else hipLaunchKernelGGL(k_emit_g2, dim3(p.nseg), dim3(64), 0, tail, lvl_in, res);
+        } else if constexpr (g1) {   // (wide, one segment: kw = 1, the fold only converts -- with a quad of lanes)
+            hipLaunchKernelGGL(k_fold_quad, dim3(1), dim3(64), 0, tail, lvl_in, p.kw, p.c, res);
+        } else {
+            hipLaunchKernelGGL(k_fold_quad_g2, dim3(1), dim3(64), 0, tail, lvl_in, p.kw, p.c, res);
+        }
+    }
+    if (!inline_tail) {
+        int rc = publish_order_large(tb, prev, tail);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, tail, (const uint32_t *)res, (uint32_t *)d_out, (unsigned)(p.nseg * sizeof(J) / 4));
+    }
+    mark(7, tail);
+    return LSA_OK;
+}
+
+static int plan_error(const PipelinePlan &p) {
+    switch (p.status) {
+    case PLAN_OK: return LSA_OK;
+    case PLAN_N_TOO_LARGE: set_error("msm: n too large (%zu)", p.n); break;
+    case PLAN_SEGMENTS_NEED_COPIES: set_error("msm: segmented calls need bases with pre-shifted copies"); break;
+    case PLAN_TABLE_TOO_LARGE: set_error("msm: base table too large for 30-bit entries"); break;
+    case PLAN_BIN_SPACE: set_error("msm: %u segments of %u buckets exceed the bin space", p.nseg, p.B); break;
+    }
+    return LSA_ERR_INVALID;
 }
 
 // The whole pipeline.  segs.nseg == 1: one MSM over n = segs.off[1] pairs.  segs.nseg > 1 (wide path
@@ -1914,331 +2111,55 @@ static int msm_pipeline(const void *d_bases_v, size_t first, const Fr *d_scalars
     using C = typename CurveOf<F>::type;
     using A = typename C::Acc;
     const typename C::Base *d_bases = (const typename C::Base *)d_bases_v + first;
-    const uint32_t nseg = segs.nseg;
-    const size_t n = segs.off[nseg];
-    if (n >= (size_t(1) << 27)) { set_error("msm: n too large (%zu)", n); return LSA_ERR_INVALID; }
-    const bool wide = table_stride != 0 && (nseg > 1 || n >= table_use_min());
-    if (nseg > 1 && !wide) { set_error("msm: segmented calls need bases with pre-shifted copies"); return LSA_ERR_INVALID; }
-    WidePlan pl = {};
-    if (wide) {
-        pl = wide_plan(table_stride, n, nseg);
-        if ((uint64_t)table_stride * table_copies(table_stride) >= (1u << 30)) { set_error("msm: base table too large for 30-bit entries"); return LSA_ERR_INVALID; }
-    }
-    const bool glv = C::GLV && !wide;
-    const unsigned c = wide ? pl.c : msm_window_bits(glv ? 2 * n : n);       // plain path: sized by the virtual scalars
-    const unsigned nwin = wide ? pl.nwin : (glv ? (128 + c - 1) / c : num_windows(c));   // |k1|,|k2| < 2^127 (glv.h)
-    const size_t nv = glv ? 2 * n : n;                                       // virtual scalars
-    const uint32_t B = 1u << (c - 1);
-    const uint32_t nb = wide ? nseg * B : nwin * B;                          // wide: one bucket space per segment, shared by all windows
-    if (wide && (uint64_t)nseg * B > (1u << 21)) { set_error("msm: %u segments of %u buckets exceed the bin space", nseg, B); return LSA_ERR_INVALID; }
-    const bool fine = wide && nb > 32768;                                    // two-pass sort
-    // 32-bit records (6 fine bits) when every point reference fits 25 bits, else 64-bit ones (7 fine bits)
-    static const bool allow_rec32 = getenv("LSA_NO_REC32") == nullptr;
-    const bool rec32 = fine && allow_rec32 && (uint64_t)table_stride * table_copies(table_stride) < (1u << 25) && (nb >> 6) <= 32768;
-    // partitioned sort (k_partition / k_fine_sort_part): one large MSM whose tile count fits the second pass's LDS
-    static const bool allow_part = getenv("LSA_NO_PART") == nullptr;
-    const bool part = fine && allow_part && nseg == 1 && nwin <= 13 && n <= ((size_t)1 << 25) && (nb & (nb - 1)) == 0 && nb >= (1u << 19);
-    const uint32_t fine_bits = rec32 ? 6u : WIDE_FINE_BITS;                  // (of the k_scatter_wide / k_fine_sort path)
-    CoarseMap cm = {0u, 0u, fine ? fine_bits : 0u, 0u};
-    uint32_t Bc = !wide ? B : (fine ? nb >> fine_bits : nb);                 // bins of the first sort pass
-    if (part) {
-        // 512 bins below B/2 and 256 above when some windows are a bit narrower than the widest
-        // (they only reach the lower half of the buckets), 512 equal bins otherwise
-        bool narrower = false;
-        for (unsigned k = 0; k < nwin; k++) narrower |= pl.width[k] < c;
-        unsigned lg = 0;
-        while ((1u << lg) < B) lg++;
-        if (narrower) { cm.half = B >> 1; cm.sh_lo = lg - 1 - 9; cm.sh_hi = lg - 1 - 8; cm.nlo = 512; Bc = 768; }
-        else { cm.half = 0; cm.sh_lo = cm.sh_hi = lg - 9; cm.nlo = 0; Bc = 512; }
-    }
-    const size_t ne = nv * nwin;
-    const bool big = wide && B > 4096;                                       // throughput-shaped reduction
-    static const uint32_t wide_split = getenv("LSA_WIDE_SPLIT") ? (uint32_t)atoi(getenv("LSA_WIDE_SPLIT")) : 1u;
-    const uint32_t split = wide ? (wide_split == 2 ? 2u : 1u) : 2u;        // lanes per bucket in k_accumulate
-    // first reduction level: quads over L buckets (latency) or, for 2^19+ buckets, lanes over L buckets (throughput)
-    // (a quad-shared first level over 2^19 buckets was measured too: 0.69 - 1.27 ms against 0.63 ms)
-    // (G2, measured in round 6 with 32768 / 16384 / 8192 first-level lanes instead of 65536 -- longer lane-private chains, a half
-    // to an eighth of the quad level's work behind them: pipelined 2^20-pair G2 MSMs 4.75-5.07 -> 4.80 / 5.41 / 6.78 ms.  65536 stays.)
-    const uint32_t L = big ? std::max<uint32_t>(1, B / 65536) : (B > 4096 ? B / 4096 : 1);
-    uint32_t logL = 0;
-    while ((1u << logL) < L) logL++;
-    const uint32_t T = B / L;                        // first-level segments per window
-    const uint32_t wpw = big ? T : (T + 15) / 16;    // (ACC,RUN) pairs per window leaving level 1
-    const uint32_t kw = wide ? nseg : nwin;          // bucket spaces ("windows") entering the reduction
-    // Buckets far above the average population (skewed scalars; the partly filled top window)
-    // are split across workgroups instead of being walked by their owner lanes.  With narrow
-    // digits every bucket is long (26*n/512 entries), and the point of that path is latency:
-    // anything above 4 entries is cut into chunks summed by a wavefront each.
-    const uint32_t avg_pop = (uint32_t)(ne / nb + 1);
-    // wide digits: the fullest buckets are those of the lower half, which every window reaches -- n / B
-    // entries from each window of the widest width, twice that from each narrower one (36 at n = 2^20, 168
-    // at n = 2^24); twice that expectation (6 sigma and more) separates them from skewed inputs, whose
-    // long single-lane lists would otherwise bound the accumulate kernel (runs of equal scalars: 3.9 -> 3.2 ms)
-    uint32_t pop_lo = avg_pop;
-    if (wide && big) {
-        unsigned nfull = 0;
-        for (unsigned k = 0; k < nwin; k++) nfull += pl.width[k] == c;
-        pop_lo = (uint32_t)(((uint64_t)n * (nfull + 2 * (nwin - nfull))) / B + 1);
-    }
-    const uint32_t heavy_threshold = (wide && !big) ? 4u : (wide ? std::max<uint32_t>(64, 2 * pop_lo + 32) : std::max<uint32_t>(64, 2 * avg_pop + 32));
-    uint32_t bin_shift = 0;                          // populations above 1024 share bins (the order only balances wavefronts)
-    while (((heavy_threshold - 1) >> bin_shift) + 1 > SIZE_BINS - 1) bin_shift++;
-    const uint32_t max_heavy = (uint32_t)std::min<size_t>(nb, ne / heavy_threshold + 1);
-    const size_t max_chunks = ne / HEAVY_CHUNK + max_heavy + 1;
-
-    // workspace carve-up
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    size_t o_hist = carve((size_t)nb * 4 + 256);     // + heavy_count word
-    size_t o_offs = carve((size_t)nb * 4);
-    const uint32_t nscan = wide ? Bc : nb;           // counters the generic scan runs over
-    const uint32_t scan_blocks = (nscan + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;   // <= 1024 since nscan <= 2^20
-    size_t o_bsum = carve((size_t)scan_blocks * 4);
-    const uint32_t ngroups = 1;
-    size_t o_bins = carve((size_t)3 * ngroups * SIZE_BINS * 4);   // bin_count | bin_start | bin_cursor
-    size_t o_perm = carve((size_t)nb * 4);
-    const uint32_t ntiles = (uint32_t)((nv + SORT_TILE - 1) / SORT_TILE);
-    const uint32_t wtile = part ? PART_TILE : wide_tile(nwin, n);
-    const uint32_t wtiles = (uint32_t)((n + wtile - 1) / wtile);             // wide path: one row per tile (all windows)
-    const size_t rows = wide ? wtiles : (size_t)nwin * ntiles;
-    size_t o_digits = carve(wide ? 0 : ne * 4);
-    size_t o_rank = carve(wide ? 0 : ne * 2);     // plain path only: the wide passes hand out positions with LDS atomics
-    const uint32_t pitch = wide ? Bc + 96 : Bc;      // elements between rows of the tile arrays (see k_tile_scan_rows)
-    size_t o_thist = carve(rows * pitch * 2);
-    size_t o_tbase = carve(rows * pitch * 4);
-    size_t o_entries = carve(ne * 4);
-    size_t o_heavy = carve((size_t)max_heavy * 4);
-    size_t o_choff = carve((size_t)(max_heavy + 2) * 4);    // chunk offsets, the chunk count, the chunk size
-    size_t o_hpart = carve(max_chunks * sizeof(A));
-    size_t o_recs = carve(fine ? ne * (part || rec32 ? 4 : 8) : 0);   // coarse-sorted records
-    size_t o_chist = carve(fine ? (size_t)Bc * 4 : 0);
-    size_t o_coffs = carve(fine ? (size_t)Bc * 4 : 0);
-    if (g_ws.ensure(off) != 0) { set_error("msm: workspace allocation of %zu bytes failed", off); return LSA_ERR_NOMEM; }
-    // tail buffers of this call parity
-    { int rcs = tail_slots_ready(); if (rcs) return rcs; }
+    const MsmShape shape = {std::is_same<C, CurveG1>::value ? 1 : 2, sizeof(A), sizeof(Jac<F>), C::GLV, segs.off[segs.nseg], segs.nseg,
+                            table_stride, blocking, reuse_sort};
+    const PipelinePlan p = plan_pipeline(shape, switches());
+    int rc = plan_error(p);
+    if (rc) return rc;
+    if (g_ws.ensure(p.front.total) != 0) { set_error("msm: workspace allocation of %zu bytes failed", p.front.total); return LSA_ERR_NOMEM; }
     // (Running the sort of call i+1 beside the accumulate of call i on a third stream was measured
     // and rejected: with enough hardware queues for real concurrency both kernels slow each other
     // down by more than the overlap gains -- 1.87 ms per step against 1.70 -- because the
     // accumulate kernel alone already fills every SIMD's issue slots and register file.)
-    TailBuf &tb = g_tail[g_slot];
-    TailBuf &prev = g_tail[(g_slot + tail_slots() - 1) % tail_slots()];
-    hipStream_t tail = (g_overlap && !blocking) ? tb.stream : st;
-    size_t toff = 0;
-    auto tcarve = [&](size_t bytes) { size_t o = toff; toff = align_up(toff + bytes, 256); return o; };
-    size_t o_buckets = tcarve((size_t)nb * split * sizeof(A));
-    size_t o_wave = tcarve((size_t)kw * wpw * 2 * sizeof(A));
-    size_t o_win = tcarve((size_t)kw * ((wpw + 15) / 16) * 2 * sizeof(A));   // reduction levels ping-pong between the two
-    size_t o_res = tcarve((size_t)nseg * sizeof(Jac<F>));                      // this call's result(s) before they are published
-    // A BLOCKING call grows only the slot it uses (round 5; before, all eight grew together: the first G2 MSM of a process --
-    // the reference's provers issue a handful, each blocking -- paid nine hipFree + hipMalloc pairs, 4 ms on a good box
-    // and tens of ms on a slow one).  Blocking calls keep re-using one slot (below), so a prover that only ever blocks
-    // grows one slot per problem size; queued callers grow a slot the first time it sees the size.
-    // A QUEUED call (the integrator's pipelined form) still grows every slot at once: its successors take the other slots
-    // within microseconds, and a new problem size then pays its allocations in one call instead of in eight.
-    for (auto &t : g_tail) {
-        if (toff <= t.ws.cap || (blocking && &t != &tb)) continue;
-        if (t.pending) HIPCHK(hipEventSynchronize(t.done));            // about to reallocate: the old tail must be finished
-        if (t.ws.ensure(toff) != 0) { set_error("msm: tail workspace allocation of %zu bytes failed", toff); return LSA_ERR_NOMEM; }
-    }
-    if (tb.pending) HIPCHK(hipStreamWaitEvent(st, tb.done, 0));        // the front may not overwrite buckets a tail still reads
-    tb.out = d_out;
-    char *tws = (char *)tb.ws.ptr;
-    char *ws = (char *)g_ws.ptr;
-    uint32_t *hist = (uint32_t *)(ws + o_hist);
-    uint32_t *heavy_count = hist + nb;
-    uint32_t *offs = (uint32_t *)(ws + o_offs);
-    uint32_t *bsum = (uint32_t *)(ws + o_bsum);
-    uint32_t *bin_count = (uint32_t *)(ws + o_bins), *bin_start = bin_count + ngroups * SIZE_BINS, *bin_cursor = bin_start + ngroups * SIZE_BINS;
-    uint32_t *perm = (uint32_t *)(ws + o_perm);
-    int32_t *digits = (int32_t *)(ws + o_digits);
-    uint16_t *rank = (uint16_t *)(ws + o_rank);
-    uint16_t *tile_hist = (uint16_t *)(ws + o_thist);
-    uint32_t *tile_base = (uint32_t *)(ws + o_tbase);
-    uint32_t *entries = (uint32_t *)(ws + o_entries);
-    A *buckets = (A *)(tws + o_buckets);
-    uint32_t *heavy_list = (uint32_t *)(ws + o_heavy);
-    uint32_t *chunk_off = (uint32_t *)(ws + o_choff);
-    A *hpart = (A *)(ws + o_hpart);
-    uint64_t *recs = (uint64_t *)(ws + o_recs);
-    uint32_t *hist_c = fine ? (uint32_t *)(ws + o_chist) : hist;       // one pass: the bins ARE the buckets
-    uint32_t *offs_c = fine ? (uint32_t *)(ws + o_coffs) : offs;
-    A *wave_out = (A *)(tws + o_wave);
-    A *window_sums = (A *)(tws + o_win);
+    if (!blocking && (rc = grow_all_tail_slots(p.tail.total)) != 0) return rc;      // growth: a queued call grows every slot, a blocking one its own
+    MsmSlot slot;
+    rc = msm_slot_begin(st, p.tail.total, d_out, &slot, blocking);
+    if (rc) return rc;
+    TailBuf &tb = g_tail[slot.index];
+    TailBuf &prev = g_tail[(slot.index + tail_slots() - 1) % tail_slots()];
+    const hipStream_t tail = slot.tail;
+    const MsmBuffers<A> b(p, g_ws.ptr, slot.ws);
 
     if (g_profile && !g_ev_ready) {
         for (auto &row : g_ev) for (auto &e : row) HIPCHK(hipEventCreate(&e));
         g_ev_ready = true;
     }
-    int evi = 0;
-    const int evslot = g_ev_calls % EV_POOL;
-    auto mark = [&](hipStream_t s_) { if (g_profile) (void)hipEventRecord(g_ev[evslot][evi++], s_); };
-
-    mark(st);  // 0
-    { int rca = msm_func_attrs(); if (rca) return rca; }
+    const Marks mark = {g_profile ? g_ev[g_ev_calls % EV_POOL] : nullptr};
+    mark(0, st);
+    rc = msm_func_attrs();
+    if (rc) return rc;
     if (reuse_sort) {
         // second MSM of a commitment pair: the entries, populations and offsets of the call just
         // issued on this stream (same scalars, same digit plan, same table stride) are still in the
         // workspace -- the sort does not depend on the bases
-        if (!wide) { set_error("msm: a shared sort needs bases with pre-shifted copies"); return LSA_ERR_INVALID; }
-        mark(st); mark(st); mark(st);  // 1..3
-    } else if (wide) {
-        const uint32_t win_stride = (uint32_t)(table_stride * pl.copy_step);
-        hipLaunchKernelGGL(k_hist_wide, dim3(wtiles), dim3(1024), (size_t)((Bc + 1) / 2) * 4, st, d_scalars, n, segs, pl, B, Bc, cm, pitch, wtile, tile_hist);
-        mark(st);  // 1
-        // (also clears the counters of the ordering stage: two memset launches less)
-        hipLaunchKernelGGL(k_tile_scan_rows, dim3((Bc + 31) / 32), dim3(1024), 0, st, tile_hist, Bc, wtiles, pitch, tile_base, hist_c, heavy_count, bin_count,
-                           (uint32_t)(3 * ngroups * SIZE_BINS));
-        mark(st);  // 2
-        if (part) {
-            hipLaunchKernelGGL(k_partition, dim3(wtiles), dim3(1024), (size_t)nwin * PART_TILE * 4, st, d_scalars, n, segs, pl, B, Bc, cm, pitch,
-                               tile_hist, hist_c, offs_c, tile_base, (uint32_t *)recs);
-            const uint32_t fixed_words = 2 * (1u << cm.sh_hi) + wtiles + 1, budget_words = 155648 / 4;
-            const uint32_t stage_cap = fixed_words + PART_STAGE <= budget_words ? PART_STAGE : 0u;   // larger problems have larger segments anyway
-            hipLaunchKernelGGL(k_fine_sort_part, dim3(Bc), dim3(1024), (size_t)(fixed_words + stage_cap) * 4, st, (const uint32_t *)recs, offs_c, hist_c,
-                               tile_base, pitch, wtiles, cm, segs, win_stride, stage_cap, entries, hist, offs);
-        } else if (rec32) {
-            hipLaunchKernelGGL(k_scatter_wide<2>, dim3(wtiles), dim3(1024), (size_t)Bc * 4, st, d_scalars, n, segs, pl, B, Bc, pitch, wtile, hist_c, offs_c, tile_base, (void *)recs, win_stride);
-            hipLaunchKernelGGL(k_fine_sort<uint32_t>, dim3(Bc), dim3(1024), 0, st, (const uint32_t *)recs, offs_c, hist_c, entries, hist, offs);
-        } else if (fine) {
-            hipLaunchKernelGGL(k_scatter_wide<1>, dim3(wtiles), dim3(1024), (size_t)Bc * 4, st, d_scalars, n, segs, pl, B, Bc, pitch, wtile, hist_c, offs_c, tile_base, (void *)recs, win_stride);
-            hipLaunchKernelGGL(k_fine_sort<uint64_t>, dim3(Bc), dim3(1024), 0, st, (const uint64_t *)recs, offs_c, hist_c, entries, hist, offs);
-        } else {
-            hipLaunchKernelGGL(k_scatter_wide<0>, dim3(wtiles), dim3(1024), (size_t)Bc * 4, st, d_scalars, n, segs, pl, B, Bc, pitch, wtile, hist_c, offs_c, tile_base, (void *)entries, win_stride);
-        }
-        mark(st);  // 3
+        if (!p.wide) { set_error("msm: a shared sort needs bases with pre-shifted copies"); return LSA_ERR_INVALID; }
+        mark(1, st); mark(2, st); mark(3, st);
     } else {
-        hipLaunchKernelGGL((k_digits<C::GLV>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, n, c, nwin, digits);
-        hipLaunchKernelGGL(k_rank, dim3(ntiles, nwin), dim3(1024), (size_t)B * 2, st, digits, nv, B, ntiles, rank, tile_hist, 0u);
-        hipLaunchKernelGGL(k_tile_scan, dim3((nb + 255) / 256), dim3(256), 0, st, tile_hist, B, ntiles, nb, tile_base, hist);
-        mark(st);  // 1
-        hipLaunchKernelGGL(k_scan_sums, dim3(scan_blocks), dim3(256), 0, st, hist, nb, bsum);
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, st, bsum, scan_blocks);
-        hipLaunchKernelGGL(k_scan_final, dim3(scan_blocks), dim3(256), 0, st, hist, bsum, nb, offs);
-        mark(st);  // 2
-        hipLaunchKernelGGL(k_scatter, dim3(ntiles, nwin), dim3(1024), (size_t)B * 4, st, digits, rank, offs, tile_base, nv, n, B, ntiles, entries, 0u);
-        mark(st);  // 3
+        launch_sort<C>(p, b, d_scalars, segs, st, mark);
     }
-    // ---- accumulate stage: bucket order, accumulation, heavy buckets
-    if (!wide || reuse_sort) {         // (the wide path's k_tile_scan_rows has cleared them)
-        HIPCHK(hipMemsetAsync(heavy_count, 0, 4, st));
-        HIPCHK(hipMemsetAsync(bin_count, 0, (size_t)3 * ngroups * SIZE_BINS * 4, st));
-    }
-    {
-        const unsigned sb = (nb + 2047) / 2048;
-        const uint32_t gsz = 0u;
-        hipLaunchKernelGGL((k_size_hist<C>), dim3(sb), dim3(256), 0, st, hist, nb, heavy_threshold, bin_count, gsz, bin_shift);
-        hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(256), 0, st, bin_count, bin_start, ngroups);
-        hipLaunchKernelGGL((k_size_scatter<C>), dim3(sb), dim3(256), 0, st, hist, nb, heavy_threshold, bin_start, bin_cursor, perm, heavy_list, heavy_count, buckets, gsz, bin_shift, split);
-    }
-    mark(st);  // 4
-    // (measured equal: 3.18 ms for the pair kernel -- 160 VGPRs, no scratch, three wavefronts per SIMD, ~18 % more
-    // instructions per addition -- against 3.09 ms for the one-lane kernel at 2^20 pairs: both are instruction-issue
-    // bound, the 316 B of scratch were never the cost.  LSA_G2_PAIR=1 selects the pair kernel.)
-    static const bool g2_pair = getenv("LSA_G2_PAIR") && getenv("LSA_G2_PAIR")[0] == '1';
-    if constexpr (std::is_same<C, CurveG2>::value) {
-        if (split == 1 && g2_pair) {
-            hipLaunchKernelGGL(k_accumulate_g2_pair, dim3((nb * 2 + 255) / 256), dim3(256), 0, st, d_bases, entries, offs, hist, perm, bin_start, buckets);
-            goto acc_done;
-        }
-        if (split == 1) {       // (the generic one-lane kernel at full occupancy -- LSA_G2_OCC1 -- lost to this one in rounds 2-4; removed)
-            hipLaunchKernelGGL(k_accumulate_g2_occ2, dim3((nb + 255) / 256), dim3(256), 0, st, d_bases, entries, offs, hist, perm, bin_start, buckets);
-            goto acc_done;
-        }
-    }
-    if (split == 1)
-        hipLaunchKernelGGL((k_accumulate<C, 1u>), dim3((nb + 255) / 256), dim3(256), 0, st, d_bases, entries, offs, hist, perm, bin_start, buckets);
-    else
-        hipLaunchKernelGGL((k_accumulate<C, 2u>), dim3((nb * 2 + 255) / 256), dim3(256), 0, st, d_bases, entries, offs, hist, perm, bin_start, buckets);
-acc_done:
-    hipLaunchKernelGGL(k_heavy_plan, dim3(1), dim3(256), 0, st, hist, heavy_list, heavy_count, chunk_off);
-    hipLaunchKernelGGL((k_accumulate_heavy<C>), dim3(4096), dim3(64), 0, st, d_bases, entries, offs, hist,
-                       heavy_list, heavy_count, chunk_off, hpart);
-    hipLaunchKernelGGL((k_heavy_finish<C>), dim3(256), dim3(64), 0, st, heavy_list, heavy_count, chunk_off, hpart, buckets, split);
-    mark(st);  // 5
-    if (tail != st) HIPCHK(hipEventRecord(tb.front_done, st));
-    const bool profile = g_profile;
-    hipEvent_t ev6 = profile ? g_ev[evslot][6] : nullptr, ev7 = profile ? g_ev[evslot][7] : nullptr;
-    const size_t res_off = o_res;
-    {
-        if (tail != st) HIPCHK(hipStreamWaitEvent(tail, tb.front_done, 0));
-        if (big)
-            hipLaunchKernelGGL((k_reduce1_lane<C>), dim3(kw * ((T + 63) / 64)), dim3(64), 0, tail, buckets, B, L, split, wave_out);
-        else
-            hipLaunchKernelGGL((k_reduce1<C>), dim3(kw * wpw), dim3(64), 0, tail, buckets, B, L, logL, wpw, split, wave_out);
-        A *lvl_in = wave_out, *lvl_out = window_sums;
-        uint32_t m = wpw, lm = big ? logL : logL + 4;    // m pairs per window, each covering 2^lm buckets
-        // one bucket space of 2^19 and more buckets: after the first 16-ary level the rest are bit trees (above)
-        static const bool allow_bits = getenv("LSA_NO_REDUCE_BITS") == nullptr;
-        // (for blocking calls only: the trees are ~45 us shorter in latency and ~1 % more work than the levels they replace,
-        // which is the wrong trade for calls whose tails hide under the next call's front)
-        const bool bits_tail = allow_bits && blocking && big && kw == 1 && nseg == 1 && m >= 4096 && (m / 16) <= 8192;
-        bool converted = false;
-        Jac<F> *res = tail != st ? (Jac<F> *)(tws + res_off) : d_out;
-        // pipelined wide calls: the first 16-ary level lane-private (k_reduce2_lane: a seventh of the quad level's work)
-        static const bool allow_lane_l1 = getenv("LSA_NO_LANE_L1") == nullptr;
-        // (G1 only: 48 sequential G2 additions are 1.2 ms of latency; and only when calls are queued back to back: the
-        // previous call's tail has not been joined by the caller since it was issued.  Decided from the CALL SEQUENCE alone
-        // -- not from whether that tail happens to be running still -- so that the same calls always add in the same order
-        // and return the same Jacobian bytes.  The second half of a commitment pair (reuse_sort) is waited for right away
-        // and would pay the lane kernel's 0.2 ms of extra latency: 6.0 -> 6.25 ms.)
-        // (G2, measured in round 6: lane-private, this level is 64 wavefronts at 256 VGPRs + 228 B of scratch and runs longer than
-        // the step it should hide under -- pipelined 2^20-pair G2 MSMs 4.76 -> 5.03 ms.  LSA_G2_LANE_L1=1 selects it all the same.)
-        static const bool g2_lane_l1 = getenv("LSA_G2_LANE_L1") != nullptr && getenv("LSA_G2_LANE_L1")[0] == '1';
-        bool lane_l1 = allow_lane_l1 && (std::is_same<C, CurveG1>::value || g2_lane_l1) && !blocking && !reuse_sort && big && kw == 1 && nseg == 1 && m >= 16384 &&
-                       tail != st && prev.pending && prev.unjoined && &prev != &tb;
-        do {                                             // at least one k_reduce2 level (it leaves the sum in slot 0)
-            const uint32_t m_out = (m + 15) / 16;
-            if (lane_l1) {
-                hipLaunchKernelGGL((k_reduce2_lane<C>), dim3((m_out + 63) / 64), dim3(64), 0, tail, lvl_in, m, m_out, lm, lvl_out);
-                lane_l1 = false;
-            } else
-            hipLaunchKernelGGL((k_reduce2<C>), dim3(kw * m_out), dim3(64), 0, tail, lvl_in, m, m_out, lm, lvl_out);
-            std::swap(lvl_in, lvl_out);
-            m = m_out;
-            lm += 4;
-            if (bits_tail && m > 1) {
-                uint32_t nbits = 0;
-                while ((1u << nbits) < m) nbits++;        // indices 0 .. m - 1
-                const uint32_t G = (m + 511) / 512;       // <= 16
-                A *part = lvl_out;                        // (the level just consumed: (nbits + 1) * G + 16 values fit its m_in * 2)
-                A *weighted = part + (size_t)(nbits + 1) * G;
-                hipLaunchKernelGGL((k_reduce_bits_a<C>), dim3(nbits + 1, G), dim3(512), 0, tail, lvl_in, m, nbits, G, part);
-                hipLaunchKernelGGL((k_reduce_bits_b<C>), dim3(nbits + 1), dim3(64), 0, tail, part, nbits, G, lm, weighted);
-                if (profile) (void)hipEventRecord(ev6, tail);  // 6
-                hipLaunchKernelGGL((k_reduce_bits_c<C>), dim3(1), dim3(64), 0, tail, weighted, nbits + 1, res);
-                converted = true;
-                break;
-            }
-        } while (m > 1);
-        if (!converted && profile) (void)hipEventRecord(ev6, tail);  // 6
-        // lvl_in[2*k] = sum of window k (pairs of (ACC,RUN): stride 2)
-        if (converted) {
-            // (the bit trees end in the Jacobian point)
-        } else if (wide && nseg > 1) {   // every segment's bucket space is a finished sum: convert
-            if constexpr (std::is_same<C, CurveG1>::value) hipLaunchKernelGGL(k_emit_g1, dim3(nseg), dim3(64), 0, tail, lvl_in, res);
-            else hipLaunchKernelGGL(k_emit_g2, dim3(nseg), dim3(64), 0, tail, lvl_in, res);
-        } else if constexpr (std::is_same<C, CurveG1>::value) {   // (wide, one segment: kw = 1, the fold only converts -- with a quad of lanes)
-            hipLaunchKernelGGL(k_fold_quad, dim3(1), dim3(64), 0, tail, lvl_in, kw, c, res);
-        } else {
-            hipLaunchKernelGGL(k_fold_quad_g2, dim3(1), dim3(64), 0, tail, lvl_in, kw, c, res);
-        }
-        if (tail != st) {
-            if (prev.pending && &prev != &tb) HIPCHK(hipStreamWaitEvent(tail, prev.done, 0));   // publish in call order
-            // ... also behind every earlier tail that writes THIS destination and is not part of that chain: the compact
-            // pipeline's tails (msm_compact.hip) write d_out themselves and only wait for tails with the same destination
-            for (int i = 0; i < NTAIL; i++) {
-                TailBuf &o = g_tail[i];
-                if (&o != &tb && &o != &prev && o.pending && o.out == (const void *)d_out) HIPCHK(hipStreamWaitEvent(tail, o.done, 0));
-            }
-            hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, tail, (const uint32_t *)res, (uint32_t *)d_out, (unsigned)(nseg * sizeof(Jac<F>) / 4));
-        }
-        if (profile) (void)hipEventRecord(ev7, tail);  // 7
-        HIPCHK(hipEventRecord(tb.done, tail));
-    }
-    tb.pending = true;
-    tb.unjoined = (tail != st);
+    rc = launch_accumulate<C>(p, b, d_bases, st, mark);
+    if (rc) return rc;
+    rc = slot_front_to_tail(tb, tail, st);
+    if (rc) return rc;
+    // The lane-private first level only when calls are queued back to back: the previous call's tail has not been joined by
+    // the caller since it was issued.  Decided from the CALL SEQUENCE alone -- not from whether that tail happens to be running
+    // still -- so that the same calls always add in the same order and return the same Jacobian bytes.
+    const bool lane_l1 = p.lane_l1_shape && tail != st && prev.pending && prev.unjoined && &prev != &tb;
+    rc = launch_tail<C>(p, b, d_out, tail, tail == st, lane_l1, tb, prev, mark);
+    if (rc) return rc;
     // a blocking caller waits for this tail before it calls again: its next call can take the same slot (and its workspace)
-    if (!blocking) g_slot = (g_slot + 1) % tail_slots();
+    rc = slot_finish(tb, tail, st, /*advance=*/!blocking);
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     if (g_profile) g_ev_calls++;
     return LSA_OK;
@@ -2260,7 +2181,7 @@ int msm_device(const void *d_bases_v, size_t first, const Fr *d_scalars, size_t 
         static const bool allow_compact = getenv("LSA_NO_COMPACT") == nullptr;
         static const bool allow_g2 = getenv("LSA_NO_COMPACT_G2") == nullptr;
         const size_t cmax = std::is_same<F, Fq>::value ? msm_compact_max() : msm_compact_max_g2();
-        if (allow_compact && (std::is_same<F, Fq>::value || allow_g2) && table_stride != 0 && n >= table_use_min() && n <= cmax)
+        if (allow_compact && (std::is_same<F, Fq>::value || allow_g2) && table_stride != 0 && n >= switches().table_use_min && n <= cmax)
             return msm_compact_device<F>(d_bases_v, first, d_scalars, n, d_out, st, table_stride, blocking);
     }
     SegList segs;
