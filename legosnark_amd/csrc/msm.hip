@@ -901,11 +901,48 @@ __global__ __launch_bounds__(256) void k_size_scatter(const uint32_t *__restrict
 // ------------------------------------------------------------------------------------
 // kernel 4: bucket accumulation (one lane per bucket); heavy buckets deferred.
 // C = curve traits (CurveG1: 29-bit limbs, 64-B packed bases; CurveG2: Fq2 on the same limbs, 128-B bases).
-// The next entry's point is fetched before the current mixed add is issued, so the
-// ~2 us gather latency hides under the ~2300 VALU instructions of a mixed addition (G1: 2 309 in the loop, DESIGN.md
-// "Bucket addition: instruction count").
+// Loads (DESIGN.md "Bucket accumulation: loads"): the loop is rotated by one entry.  Iteration j holds entry word j+1
+// already; at its top it issues, unconditionally, the load of entry word j+2 and the gather of base j+1, and it consumes
+// that base only in iteration j+1 -- so the gather (an HBM round trip into a table of up to 872 MB) and the dependent
+// index load before it have a whole mixed addition (G1: 2 293 instructions in the loop) to arrive in.  A lane past its end
+// loads a clamped index, the last entry of its own part: no lane reads outside its list or a base its list does not name.
+// (A load under `if (j + 1 < cnt)` made the compiler wait for it inside the branch, ahead of the addition.)
 // ------------------------------------------------------------------------------------
-template <class C, uint32_t ACC_SPLIT>
+// A packed base as 16-byte vectors.  The 64 / 128-B records lie on 64-B boundaries (whole records of a hipMalloc'd
+// table); the structs only promise 4, and unpack256 reads overlapping 64-bit pairs of words, from which the compiler
+// made overlapping x3 / x4 / x2 / x1 loads.  load_base16 requests the vectors; packed_base, called where the base is
+// consumed, hands them over as the packed struct.  Its empty asm uses every vector whole, so the loads stay four (eight)
+// global_load_dwordx4 and the wait for them stays at the use.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <class B> struct RawBase {
+    static_assert(sizeof(B) % 16 == 0, "packed bases are whole 16-byte vectors");
+    u32x4 q[sizeof(B) / 16];
+};
+template <class B>
+__device__ __forceinline__ RawBase<B> load_base16(const B *__restrict__ p) {
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(p);
+    RawBase<B> r;
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(B) / 16); i++) r.q[i] = src[i];
+    return r;
+}
+template <class B>
+__device__ __forceinline__ B packed_base(RawBase<B> r) {
+    B b;
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&b);
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(B) / 16); i++) {
+        asm("" : "+v"(r.q[i]));
+        dst[4 * i] = r.q[i].x; dst[4 * i + 1] = r.q[i].y; dst[4 * i + 2] = r.q[i].z; dst[4 * i + 3] = r.q[i].w;
+    }
+    return b;
+}
+// Which curves take the rotated loop.  G2 keeps the loop it had: rotated, k_accumulate_g2_occ2 needs 368 B of scratch per
+// lane instead of 316 at its 256 VGPRs and k_accumulate<CurveG2, 2> 256 + 48 registers instead of 256 + 43 (the extra
+// entry word and eight 16-byte destinations on top of a register file that is full already).
+template <class C> struct RotatedLoads { static constexpr bool value = true; };
+template <> struct RotatedLoads<CurveG2> { static constexpr bool value = false; };
+template <class C, uint32_t ACC_SPLIT, bool ROTATED = RotatedLoads<C>::value>
 __device__ __forceinline__ void accumulate_body(const typename C::Base *__restrict__ bases, const uint32_t *__restrict__ entries,
                                                 const uint32_t *__restrict__ offs, const uint32_t *__restrict__ hist,
                                                 const uint32_t *__restrict__ perm, const uint32_t *__restrict__ nperm,
@@ -920,33 +957,52 @@ __device__ __forceinline__ void accumulate_body(const typename C::Base *__restri
     // One lane per bucket is the wide path only, whose entries never carry the endo bit: no beta multiplication in that loop.
     constexpr bool ENDO = ACC_SPLIT != 1;
     typename C::Acc acc = C::inf();
-    if (part < cnt) {
-        uint32_t v = e[part];
-        typename C::Base cur = bases[v & 0x3fffffffu];
+    if constexpr (!ROTATED) {
+        if (part < cnt) {
+            uint32_t v = e[part];
+            typename C::Base cur = bases[v & 0x3fffffffu];
+            static_assert(!C::HEAD || ROTATED, "the affine + affine head is written for the rotated loop only");
+            for (uint32_t j = part; j < cnt; j += ACC_SPLIT) {
+                uint32_t vn = v;
+                typename C::Base nxt = cur;
+                if (j + ACC_SPLIT < cnt) { vn = e[j + ACC_SPLIT]; nxt = bases[vn & 0x3fffffffu]; }
+                acc = C::template madd<ENDO>(acc, cur, (v >> 31) != 0, ((v >> 30) & 1) != 0);
+                v = vn;
+                cur = nxt;
+            }
+        }
+    } else if (part < cnt) {
+        const uint32_t last = part + (cnt - 1 - part) / ACC_SPLIT * ACC_SPLIT;      // this lane's last entry
+        auto word = [&](uint32_t k) { return e[k < last ? k : last]; };
+        auto base = [&](uint32_t w) { return load_base16(bases + (w & 0x3fffffffu)); };
         uint32_t j = part;
+        uint32_t v = word(j), vn = word(j + ACC_SPLIT);
+        RawBase<typename C::Base> cur;
         if constexpr (C::HEAD) {
             // The first two entries as affine + affine.  A list of one entry, or an infinity base among the two, takes
             // the loop from the start: there an accumulator at infinity is the rare path of the mixed addition.
-            if (j + ACC_SPLIT < cnt) {
-                const uint32_t v1 = e[j + ACC_SPLIT];
-                const typename C::Base b1 = bases[v1 & 0x3fffffffu];
-                if (C::head_ok(cur, b1)) {
-                    uint32_t vn = v1;
-                    typename C::Base nxt = b1;
-                    if (j + 2 * ACC_SPLIT < cnt) { vn = e[j + 2 * ACC_SPLIT]; nxt = bases[vn & 0x3fffffffu]; }
-                    acc = C::template madd_head<ENDO>(cur, (v >> 31) != 0, ((v >> 30) & 1) != 0, b1, (v1 >> 31) != 0, ((v1 >> 30) & 1) != 0);
-                    j += 2 * ACC_SPLIT;
-                    v = vn;
-                    cur = nxt;
-                }
+            // Entry words 0 .. 3 and the bases of entries 0 .. 2 are requested here, unconditionally; the compiler moves the
+            // requests that only the head uses (words 2, 3, base 2) into its branch, in front of the head's arithmetic.
+            const uint32_t v2 = word(j + 2 * ACC_SPLIT), v3 = word(j + 3 * ACC_SPLIT);
+            const RawBase<typename C::Base> r0 = base(v), r1 = base(vn), r2 = base(v2);
+            const typename C::Base b0 = packed_base(r0), b1 = packed_base(r1);
+            cur = r0;
+            if (j + ACC_SPLIT < cnt && C::head_ok(b0, b1)) {
+                acc = C::template madd_head<ENDO>(b0, (v >> 31) != 0, ((v >> 30) & 1) != 0, b1, (vn >> 31) != 0, ((vn >> 30) & 1) != 0);
+                j += 2 * ACC_SPLIT;
+                v = v2;
+                vn = v3;
+                cur = r2;
             }
+        } else {
+            cur = base(v);
         }
         for (; j < cnt; j += ACC_SPLIT) {
-            uint32_t vn = v;
-            typename C::Base nxt = cur;
-            if (j + ACC_SPLIT < cnt) { vn = e[j + ACC_SPLIT]; nxt = bases[vn & 0x3fffffffu]; }
-            acc = C::template madd<ENDO>(acc, cur, (v >> 31) != 0, ((v >> 30) & 1) != 0);
+            const uint32_t vnn = word(j + 2 * ACC_SPLIT);
+            const RawBase<typename C::Base> nxt = base(vn);
+            acc = C::template madd<ENDO>(acc, packed_base(cur), (v >> 31) != 0, ((v >> 30) & 1) != 0);
             v = vn;
+            vn = vnn;
             cur = nxt;
         }
     }
@@ -1092,9 +1148,26 @@ __global__ __launch_bounds__(64) void k_accumulate_heavy(const typename C::Base 
         const uint32_t end = start + chunk < cnt ? start + chunk : cnt;
         const uint32_t *e = entries + offs[g];
         typename C::Acc acc = C::inf();
-        for (uint32_t j = start + lane; j < end; j += 64) {
-            uint32_t w = e[j];
-            acc = C::madd(acc, bases[w & 0x3fffffffu], (w >> 31) != 0, ((w >> 30) & 1) != 0);
+        uint32_t j = start + lane;
+        if constexpr (!RotatedLoads<C>::value) {
+            for (; j < end; j += 64) {
+                uint32_t w = e[j];
+                acc = C::madd(acc, bases[w & 0x3fffffffu], (w >> 31) != 0, ((w >> 30) & 1) != 0);
+            }
+        } else if (j < end) {
+            // the same rotation as accumulate_body, stride 64 inside the chunk, clamped to this lane's last entry of it
+            const uint32_t last = j + (end - 1 - j) / 64 * 64;
+            auto word = [&](uint32_t k) { return e[k < last ? k : last]; };
+            uint32_t w = word(j), wn = word(j + 64);
+            RawBase<typename C::Base> cur = load_base16(bases + (w & 0x3fffffffu));
+            for (; j < end; j += 64) {
+                const uint32_t wnn = word(j + 128);
+                const RawBase<typename C::Base> nxt = load_base16(bases + (wn & 0x3fffffffu));
+                acc = C::madd(acc, packed_base(cur), (w >> 31) != 0, ((w >> 30) & 1) != 0);
+                w = wn;
+                wn = wnn;
+                cur = nxt;
+            }
         }
         acc = wave_sum<C>(acc, lane);
         if (lane == 0) partials[v] = acc;
