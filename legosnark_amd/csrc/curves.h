@@ -29,7 +29,13 @@ struct CurveG1 {
     static __device__ __forceinline__ Acc madd_head(const Base &b0, bool neg0, bool endo0, const Base &b1, bool neg1, bool endo1) {
         return g1_madd_head<ENDO>(b0, neg0, endo0, b1, neg1, endo1);
     }
-    static __device__ __forceinline__ Acc add(const Acc &a, const Acc &b) { return xyzz29_add(a, b); }
+    // PAIRED: the general addition with its products in pairs (fp29.h: xyzz29_add_paired), for the kernels whose registers
+    // allow it -- msm.hip names them through PairedAdd below
+    template <bool PAIRED = false>
+    static __device__ __forceinline__ Acc add(const Acc &a, const Acc &b) {
+        if constexpr (PAIRED) return xyzz29_add_paired(a, b);
+        else return xyzz29_add(a, b);
+    }
     static __device__ __forceinline__ Acc dbl(const Acc &a) { return xyzz29_dbl(a); }
     static __device__ __forceinline__ Jac<Fq> to_jac(const Acc &a) { return xyzz29_to_jac(a); }
     static __device__ __forceinline__ Acc from_jac(const Jac<Fq> &p) {          // ZZ = Z^2, ZZZ = Z^3
@@ -66,6 +72,7 @@ struct CurveG2 {
         if (negate) q.y = sub_k<1>(F29x2::zero(), q.y);                // p - y per component
         return g2_madd(a, q);
     }
+    template <bool PAIRED = false>      // unused: G2 has one general addition
     static __device__ __forceinline__ Acc add(const Acc &a, const Acc &b) { return g2_add(a, b); }
     static __device__ __forceinline__ Acc dbl(const Acc &a) { return g2_dbl(a); }
     static __device__ __forceinline__ Jac<Fq2> to_jac(const Acc &a) { return g2_to_jac(a); }

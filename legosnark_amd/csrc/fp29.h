@@ -17,6 +17,7 @@
 // Device-resident bases and buckets use this form; conversion from/to libff's layout
 // (8 x 32-bit limbs, R = 2^256) happens once at the boundary (from_mont256 / to_mont256).
 #pragma once
+#include <utility>
 #include "ec.h"
 
 namespace lsa {
@@ -464,6 +465,127 @@ LSA_HD F29 sub_loose(const F29 &a, const F29 &b) {
 }
 
 // ------------------------------------------------------------------------------------
+// Paired products: two independent Montgomery products (two mul or two sqr) stepped column by column side by side, each
+// in ONE 64-bit accumulator chain.  Left to itself the compiler opens every column of mul() in a fresh
+// accumulator and re-adds the shifted carry (16 v_lshl_add_u64 per product, each as dear as a multiply-add) to keep
+// dependent v_mad_u64_u32 apart; with two chains interleaved the neighbour's step stands between two dependent ones and
+// the re-adds go.  The column sums are the same integers as in the single forms, only the order of the additions within a
+// column differs, so every operand bound written next to mul / sqr holds unchanged and the results are identical limb
+// for limb.  Both chains of a pair have the same number of steps in every column: a chain that steps alone pays the wait
+// state below on every step, which is why dot2 (twice the terms of its neighbour) keeps its own form.
+//
+// The step is plain C++ with an empty asm statement on the accumulator (the compiler can then neither reassociate the chain
+// nor open a fresh accumulator) and a scheduling barrier behind it: the hazard recognizer wants a wait state between an asm
+// statement, an empty one too, and the next instruction that reads its operand, and without the barrier the scheduler emits
+// A, B, asm, asm, s_nop, A.  Pinned to the source order -- A, asm, B, asm, A -- the neighbour's step is that wait state
+// (tools/ubench_int.hip: 177-180 G products/s against 167-169 for two mul() at three wavefronts per SIMD).
+//
+// A term source lists the limb products of its form: count(k) of them in column k, term s of column k added by term().
+struct MacPaired {
+    static LSA_HD void mac(uint64_t &acc, uint32_t a, uint32_t b) {
+        acc += (uint64_t)a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(acc));
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
+};
+struct MulTerms {
+    const F29 &a, &b;
+    static constexpr int count(int k) { return k < 9 ? k + 1 : 17 - k; }
+    template <class Mac>
+    LSA_HD void term(uint64_t &acc, int k, int s) const {
+        const int i = (k < 9 ? 0 : k - 8) + s;
+        Mac::mac(acc, a.l[i], b.l[k - i]);
+    }
+};
+// a^2 as in sqr(): cross terms once against the doubled limbs d, then the square of the middle limb in even columns
+struct SqrTerms {
+    const F29 &a;
+    const uint32_t (&d)[9];
+    static constexpr int lo(int k) { return k < 9 ? 0 : k - 8; }
+    static constexpr int cross(int k) { return (k + 1) / 2 - lo(k); }          // i in [lo, ceil(k/2)): j = k - i > i
+    static constexpr int count(int k) { return cross(k) + ((k & 1) == 0 ? 1 : 0); }
+    template <class Mac>
+    LSA_HD void term(uint64_t &acc, int k, int s) const {
+        if (s < cross(k)) Mac::mac(acc, a.l[lo(k) + s], d[k - lo(k) - s]);
+        else Mac::mac(acc, a.l[k / 2], a.l[k / 2]);
+    }
+};
+struct F29Pair {
+    F29 a, b;
+};
+// the one column stepper: chain 0 over the terms of t0, chain 1 over those of t1, step by step in turn.  The column index
+// is a template parameter so that every limb index is a constant before the loops are unrolled.
+template <class Mac, class T0, class T1>
+struct F29Chain2 {
+    uint64_t acc0 = 0, acc1 = 0;
+    uint32_t m0[9], m1[9];
+    F29Pair r;
+    template <int K>
+    LSA_HD void column(const T0 &t0, const T1 &t1) {
+        constexpr int N0 = T0::count(K), N1 = T1::count(K), N = N0 > N1 ? N0 : N1;
+#pragma unroll
+        for (int s = 0; s < N; s++) {
+            if (s < N0) t0.template term<Mac>(acc0, K, s);
+            if (s < N1) t1.template term<Mac>(acc1, K, s);
+        }
+#pragma unroll
+        for (int i = (K < 9 ? 0 : K - 8); i < (K < 9 ? K : 9); i++) {
+            Mac::mac(acc0, m0[i], F29::p(K - i));
+            Mac::mac(acc1, m1[i], F29::p(K - i));
+        }
+        if constexpr (K < 9) {
+            m0[K] = ((uint32_t)acc0 * F29::PINV) & F29::MASK;
+            m1[K] = ((uint32_t)acc1 * F29::PINV) & F29::MASK;
+            Mac::mac(acc0, m0[K], F29::p(0));
+            Mac::mac(acc1, m1[K], F29::p(0));
+        } else {
+            r.a.l[K - 9] = (uint32_t)acc0 & F29::MASK;
+            r.b.l[K - 9] = (uint32_t)acc1 & F29::MASK;
+        }
+        acc0 >>= 29;
+        acc1 >>= 29;
+    }
+    template <int... K>
+    LSA_HD void columns(const T0 &t0, const T1 &t1, std::integer_sequence<int, K...>) {
+        (column<K>(t0, t1), ...);
+    }
+};
+template <class Mac, class T0, class T1>
+LSA_HD F29Pair f29_chain2(const T0 &t0, const T1 &t1) {
+    F29Chain2<Mac, T0, T1> c;
+    c.columns(t0, t1, std::make_integer_sequence<int, 17>{});
+    c.r.a.l[8] = (uint32_t)c.acc0;
+    c.r.b.l[8] = (uint32_t)c.acc1;
+    return c.r;
+}
+LSA_HD void f29_doubled(const F29 &a, uint32_t (&d)[9]) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) d[i] = a.l[i] << 1;
+}
+
+// {a0*b0, a1*b1}: bounds of mul for each.  On the host the single forms (they are the yardstick there).
+LSA_HD F29Pair mul2(const F29 &a0, const F29 &b0, const F29 &a1, const F29 &b1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return f29_chain2<MacPaired>(MulTerms{a0, b0}, MulTerms{a1, b1});
+#else
+    return {mul(a0, b0), mul(a1, b1)};
+#endif
+}
+// {a0^2, a1^2}: bounds of sqr for each (loose limbs < 2^30 allowed)
+LSA_HD F29Pair sqr2(const F29 &a0, const F29 &a1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t d0[9], d1[9];
+    f29_doubled(a0, d0);
+    f29_doubled(a1, d1);
+    return f29_chain2<MacPaired>(SqrTerms{a0, d0}, SqrTerms{a1, d1});
+#else
+    return {sqr(a0), sqr(a1)};
+#endif
+}
+
+// ------------------------------------------------------------------------------------
 // points over F29.  Invariants of an accumulator (X,Y,ZZ,ZZZ), all limbs tight:
 //     X < 8p,  Y < 4p,  ZZ < 2p,  ZZZ < 2p;  infinity <=> ZZ has all limbs zero.
 // Infinity is only ever written as XYZZ29::inf(), ALL FOUR coordinates literal zeros (xyzz29_madd_signed relies on X and Y).
@@ -547,19 +669,19 @@ LSA_HD XYZZ29 xyzz29_madd_rare(const XYZZ29 &a, const Aff29 &b, uint32_t m, cons
     if (R.is_zero_mod_p()) return xyzz29_dbl_affine(q);
     return XYZZ29::inf();
 }
+//  - the products go in pairs (mul2 / sqr2: the same limbs as mul / sqr), the dot2 alone.
 LSA_HD XYZZ29 xyzz29_madd_signed(const XYZZ29 &a, const Aff29 &b, uint32_t m) {
-    F29 U2 = mul(b.x, a.ZZ);                       // [<2p]
-    F29 S2 = mul(b.y, a.ZZZ);                      // [<2p]  (of the stored y)
-    F29 Pd = sub_k<8>(U2, a.X);                    // U2 - X1 + 8p      [<10p]
-    F29 R = sub_k_signed<6>(S2, a.Y, m);           // (+-)S2 - Y1 + 6p  [<8p]
+    const F29Pair us = mul2(b.x, a.ZZ, b.y, a.ZZZ);      // U2, S2 (of the stored y)  [<2p]
+    F29 Pd = sub_k<8>(us.a, a.X);                  // U2 - X1 + 8p      [<10p]
+    F29 R = sub_k_signed<6>(us.b, a.Y, m);         // (+-)S2 - Y1 + 6p  [<8p]
     if (Pd.is_zero_mod_p()) return xyzz29_madd_rare(a, b, m, R);
-    F29 PP = sqr(Pd);
-    F29 PPP = mul(Pd, PP);
-    F29 Q = mul(a.X, PP);
-    F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));          // R^2 - PPP - 2Q + 6p  [<8p]
+    const F29Pair sq = sqr2(Pd, R);                // PP, R^2
+    const F29Pair pq = mul2(Pd, sq.a, a.X, sq.a);  // PPP, Q
+    F29 X3 = sub_k<6>(sq.b, add_lazy(pq.a, add_lazy(pq.b, pq.b)));     // R^2 - PPP - 2Q + 6p  [<8p]
     // R(Q - X3 + 10p) + (6p - Y1)PPP: 8 * 12 + 6 * 2 = 108 p^2 < 169 p^2  [<2p];  X3 < 8p <= 9p and Y1 < 4p <= 5p (sub_loose)
-    F29 Y3 = dot2(R, sub_loose<10>(Q, X3), sub_loose<6>(F29::zero(), a.Y), PPP);
-    return {X3, Y3, mul(a.ZZ, PP), mul(a.ZZZ, PPP)};
+    F29 Y3 = dot2(R, sub_loose<10>(pq.b, X3), sub_loose<6>(F29::zero(), a.Y), pq.a);
+    const F29Pair zz = mul2(a.ZZ, sq.a, a.ZZZ, pq.a);    // ZZ * PP, ZZZ * PPP
+    return {X3, Y3, zz.a, zz.b};
 }
 
 // (x1, y1) + s * (x2, y2), both affine and neither infinity: the head of a bucket list.  With ZZ1 = ZZZ1 = 1 the four
@@ -574,13 +696,12 @@ LSA_HD XYZZ29 xyzz29_add_affine(const Aff29 &a, const Aff29 &b, uint32_t m) {
         if (m) q.y = sub_k<1>(F29::zero(), b.y);
         return xyzz29_dbl_affine(q);
     }
-    F29 PP = sqr(Pd);
-    F29 PPP = mul(Pd, PP);
-    F29 Q = mul(a.x, PP);
-    F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));          // [<8p]
+    const F29Pair sq = sqr2(Pd, R);                // PP, R^2
+    const F29Pair pq = mul2(Pd, sq.a, a.x, sq.a);  // PPP, Q
+    F29 X3 = sub_k<6>(sq.b, add_lazy(pq.a, add_lazy(pq.b, pq.b)));     // [<8p]
     // R(Q - X3 + 10p) + (3p - y1)PPP: 3 * 12 + 3 * 2 = 42 p^2  [<2p];  y1 <= p < 2p (sub_loose)
-    F29 Y3 = dot2(R, sub_loose<10>(Q, X3), sub_loose<3>(F29::zero(), a.y), PPP);
-    return {X3, Y3, PP, PPP};
+    F29 Y3 = dot2(R, sub_loose<10>(pq.b, X3), sub_loose<3>(F29::zero(), a.y), pq.a);
+    return {X3, Y3, sq.a, pq.a};
 }
 
 // a + b, complete (add-2008-s).  Inputs and output within the accumulator invariants.
@@ -603,6 +724,27 @@ LSA_HD XYZZ29 xyzz29_add(const XYZZ29 &a, const XYZZ29 &b) {
     F29 X3 = sub_k<6>(sqr(R), add_lazy(PPP, add_lazy(Q, Q)));
     F29 Y3 = dot2(R, sub_k<8>(Q, X3), sub_k<2>(F29::zero(), S1), PPP);    // R(Q-X3) + (2p-S1)PPP: 40 + 4  [<2p]
     return {X3, Y3, mul(mul(a.ZZ, b.ZZ), PP), mul(mul(a.ZZZ, b.ZZZ), PPP)};
+}
+// The same addition with its products in pairs (mul2 / sqr2: the same limbs as mul / sqr), the dot2 alone; the rare paths
+// keep the single forms.  For the kernels that CurveG1's PairedAdd trait names (curves.h).
+LSA_HD XYZZ29 xyzz29_add_paired(const XYZZ29 &a, const XYZZ29 &b) {
+    if (b.is_inf()) return a;
+    if (a.is_inf()) return b;
+    const F29Pair u = mul2(a.X, b.ZZ, b.X, a.ZZ);        // U1, U2
+    const F29Pair v = mul2(a.Y, b.ZZZ, b.Y, a.ZZZ);      // S1, S2
+    F29 Pd = sub_k<2>(u.b, u.a);                   // [<4p]
+    F29 R = sub_k<2>(v.b, v.a);
+    if (Pd.is_zero_mod_p()) {
+        if (R.is_zero_mod_p()) return xyzz29_dbl(a);
+        return XYZZ29::inf();
+    }
+    const F29Pair sq = sqr2(Pd, R);                // PP, R^2
+    const F29Pair pq = mul2(Pd, sq.a, u.a, sq.a);  // PPP, Q
+    F29 X3 = sub_k<6>(sq.b, add_lazy(pq.a, add_lazy(pq.b, pq.b)));
+    F29 Y3 = dot2(R, sub_k<8>(pq.b, X3), sub_k<2>(F29::zero(), v.a), pq.a);    // R(Q-X3) + (2p-S1)PPP: 40 + 4  [<2p]
+    const F29Pair z = mul2(a.ZZ, b.ZZ, a.ZZZ, b.ZZZ);
+    const F29Pair zz = mul2(z.a, sq.a, z.b, pq.a);
+    return {X3, Y3, zz.a, zz.b};
 }
 
 // ---- the two operations of the G1 bucket accumulation on packed, stored bases (curves.h: CurveG1) ----

@@ -1078,12 +1078,22 @@ __device__ __forceinline__ A shfl_down_acc(const A &p, unsigned delta) {
     return r;
 }
 
+// Which kernels of the tail run CurveG1's general addition with its products in pairs (curves.h: add<true>): those that keep
+// their register limits with it -- three wavefronts per SIMD and no scratch for k_accumulate_heavy, the parent's 231 VGPRs
+// for k_reduce1_lane, its 256 + 12 for k_reduce2_lane (profiles/r09_paired_products.txt has the compiled figures).
+enum TailKernel { TAIL_HEAVY, TAIL_REDUCE1_LANE, TAIL_REDUCE2_LANE };
+template <class C, TailKernel K> struct PairedAdd { static constexpr bool value = false; };
+template <> struct PairedAdd<CurveG1, TAIL_HEAVY> { static constexpr bool value = true; };
+template <> struct PairedAdd<CurveG1, TAIL_REDUCE1_LANE> { static constexpr bool value = true; };
+// k_reduce2_lane compiles to 256 VGPRs + 14 AGPRs with it, against 256 + 12: it stays on xyzz29_add (the two AGPRs cost it
+// 10 % once before, DESIGN.md "Bucket addition: instruction count")
+
 // wavefront tree sum: result valid in lane 0
-template <class C>
+template <class C, bool PAIRED = false>
 __device__ __forceinline__ typename C::Acc wave_sum(typename C::Acc v, unsigned lane) {
     for (unsigned d = 32; d >= 1; d >>= 1) {
         typename C::Acc t = shfl_down_acc(v, d);
-        if (lane + d < 64) v = C::add(v, t);
+        if (lane + d < 64) v = C::template add<PAIRED>(v, t);
     }
     return v;
 }
@@ -1169,7 +1179,7 @@ __global__ __launch_bounds__(64) void k_accumulate_heavy(const typename C::Base 
                 cur = nxt;
             }
         }
-        acc = wave_sum<C>(acc, lane);
+        acc = wave_sum<C, PairedAdd<C, TAIL_HEAVY>::value>(acc, lane);
         if (lane == 0) partials[v] = acc;
     }
 }
@@ -1273,7 +1283,7 @@ __global__ __launch_bounds__(64) void k_reduce1_lane(const typename C::Acc *__re
             A rhs = run;
             if (h < split) rhs = bk[(size_t)i * split + h];
             const A lhs = select_acc(m, run, acc);
-            const A r = C::add(lhs, rhs);
+            const A r = C::template add<PairedAdd<C, TAIL_REDUCE1_LANE>::value>(lhs, rhs);
             run = select_acc(m, r, run);
             acc = select_acc(m, acc, r);
         }
@@ -1310,7 +1320,7 @@ __global__ __launch_bounds__(64) void k_reduce2_lane(const typename C::Acc *__re
             A rhs = run;                                                    // h == 2: wsum += run
             if (h < 2) rhs = have ? in[2 * (size_t)idx + h] : A::inf();
             const A lhs = select_acc(m0, acc, select_acc(m1, run, wsum));
-            const A r = C::add(lhs, rhs);
+            const A r = C::template add<PairedAdd<C, TAIL_REDUCE2_LANE>::value>(lhs, rhs);
             acc = select_acc(m0, r, acc);
             run = select_acc(m1, r, run);
             wsum = select_acc(~(m0 | m1), r, wsum);
@@ -1318,7 +1328,7 @@ __global__ __launch_bounds__(64) void k_reduce2_lane(const typename C::Acc *__re
     }
 #pragma unroll 1
     for (uint32_t i = 0; i < log_mult; i++) wsum = C::dbl(wsum);
-    out[2 * (size_t)t] = C::add(acc, wsum);
+    out[2 * (size_t)t] = C::template add<PairedAdd<C, TAIL_REDUCE2_LANE>::value>(acc, wsum);
     out[2 * (size_t)t + 1] = run;
 }
 
