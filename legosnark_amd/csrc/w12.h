@@ -181,7 +181,22 @@ LSA_HD F29 w12_comp_mul_lift(unsigned part, const Fq2S &a, const Fq2S &b, const 
     for (int l = 0; l < 7; l++) nb1.l[l] = lw[l] - b.c1.v.l[l];
     const int32_t v7 = (int32_t)lw[7] - (int32_t)b.c1.v.l[7];
     nb1.l[7] = (uint32_t)v7 & F29::MASK;
-    nb1.l[8] = (uint32_t)((int32_t)lw[8] - (int32_t)b.c1.v.l[8] + (v7 >> 29));
+    const int32_t v8 = (int32_t)lw[8] - (int32_t)b.c1.v.l[8] + (v7 >> 29);
+    nb1.l[8] = (uint32_t)v8;
+    // The lift lends 2^203 from limbs 7 and 8: for b1 in the last (K p mod 2^203) below K p -- about 2^-52 of the values the contract
+    // allows -- they have nothing left to lend and limb 8 comes out as -1.  There K p - b1 < 2^204, so p is added on top (limbs below
+    // 3 * 2^29, which dot2 takes beside a tight partner; a1 * (p + 2^204) stays far below the a1 * K p of the bound).  One comparison
+    // and a branch the whole wavefront takes together, practically never.  (tests/cpp/test_w12_edges.cc: b1 = K p - 1)
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_amdgcn_ballot_w64(v8 < 0) != 0)
+#else
+    if (v8 < 0)
+#endif
+    {
+        const uint32_t neg = (uint32_t)(v8 >> 31);
+#pragma unroll
+        for (int l = 0; l < 9; l++) nb1.l[l] += F29::p(l) & neg;
+    }
     F29 y0, y1;
 #pragma unroll
     for (int l = 0; l < 9; l++) {
@@ -238,6 +253,12 @@ LSA_HD const W12SqRow &w12_sq_row(unsigned type, unsigned part) {
     return ROWS[type * 2 + part];
 }
 
+// The b-side combinations of the one-phase product below (w12_rows): R = c0 * b_j0 + c1 * b_j1 + K p, one signed byte
+// each at bit 8 * (4 * wrapped + 2 * part + h) -- outside the device-only block so that the host tests read the same words:
+//   plain:    part 0: (1, 0, 0), (0, -1, 2)       part 1: (0, 1, 0), (1, 0, 0)
+//   wrapped:  part 0: (9, -1, 2), (-1, -9, 20)    part 1: (1, 9, 0), (9, -1, 2)
+static constexpr uint64_t W12_ROW_C0 = 0x0901ff0901000001ull, W12_ROW_C1 = 0xff09f7ff0001ff00ull, W12_ROW_K = 0x0200140200000200ull;
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // ------------------------------------------------------------------------------------------------------------------
 // The Fq12 product in ONE phase (device only; W12::mul takes it when the workgroup has 192 lanes).  The two-phase
@@ -249,10 +270,14 @@ LSA_HD const W12SqRow &w12_sq_row(unsigned type, unsigned part) {
 // i + j >= 6 carry the factor xi = 9 + u on the b side):
 //   part 0:  a_i0 * ( b0)        + a_i1 * (-b1)          wrapped:  a_i0 * (9 b0 - b1)  + a_i1 * (-b0 - 9 b1)
 //   part 1:  a_i0 * ( b1)        + a_i1 * ( b0)          wrapped:  a_i0 * (b0 + 9 b1)  + a_i1 * (9 b0 - b1)
-// (R made non-negative with a multiple of p: < 22p).  The lane carries its columns into 18 tight limbs, the row adds
-// them up with four DPP butterfly steps (one carry pass in the middle keeps the sums in 32 bits), and every lane of the
-// row runs the ONE Montgomery reduction of the sum: T < 12 * 44 p^2 gives < 4p, one conditional subtraction < 2p.
-// ~550 instructions, one barrier (two when the destination aliases an operand).
+// (R made non-negative with a multiple of p, W12_ROW_K below: plain R <= 2p, wrapped R <= 20p).  The lane carries its
+// columns into 18 tight limbs, the row adds them up with three DPP steps (sums of eight tight limbs: < 2^32) and takes
+// the other half of the row into the 64-bit columns of the ONE Montgomery reduction, which every lane of the row runs.
+// Operands < 2p: row k has 2 (5 - k) wrapped lanes at 2p * 20p and 2 (k + 1) plain ones at 2p * 2p, so
+//   T <= 10 * 40 p^2 + 2 * 4 p^2 = 408 p^2  (row k = 0),   T / 2^261 + p < 3.42 p < 4p   (2^261 / p > 169.2),
+// and one conditional subtraction leaves < 2p.  tests/cpp/test_w12_edges.cc builds T from the packed words below at the
+// limb maxima and asserts the bound and the columns.  ~550 instructions, one barrier (two when the destination aliases
+// an operand).
 // ------------------------------------------------------------------------------------------------------------------
 // t.l[q] += t.l[q] of the lane the permutation names, all 18 limbs: one v_add_u32_dpp each, written as ONE asm block (the
 // intrinsic leaves a v_mov per limb behind; inside the block consecutive instructions touch different registers, the
@@ -415,10 +440,8 @@ __device__ __forceinline__ void w12_rows(Fq2S *D, const Fq2S *A, const Fq2S *B, 
         const unsigned iw = i < 6 ? i : 0;
         const bool wrapped = iw > k;
         const unsigned j = k - iw + (wrapped ? 6u : 0u);
-        // R = c0 * b_j0 + c1 * b_j1 + K p, the three small integers looked up by (wrapped, part, h) in packed bytes:
-        //   plain:    part 0: (1, 0, 0), (0, -1, 2)       part 1: (0, 1, 0), (1, 0, 0)
-        //   wrapped:  part 0: (9, -1, 2), (-1, -9, 20)    part 1: (1, 9, 0), (9, -1, 2)
-        // (all zero for lanes 12..15 of a row: they add nothing)
+        // R = c0 * b_j0 + c1 * b_j1 + K p, the three small integers looked up by (wrapped, part, h) in packed bytes
+        // (W12_ROW_C0 / C1 / K above; all zero for lanes 12..15 of a row: they add nothing)
         const unsigned sh = 8u * ((wrapped ? 4u : 0u) | (part << 1) | h);
         int lv = r < 12 ? -1 : 0;
         unsigned jb = j;
@@ -426,7 +449,7 @@ __device__ __forceinline__ void w12_rows(Fq2S *D, const Fq2S *A, const Fq2S *B, 
             lv &= (j == 0 || j == 3 || j == 4) ? -1 : 0;
             jb = j == 0 ? 0u : (j == 3 ? 1u : 2u);
         }
-        const int c0 = (int)(int8_t)(0x0901ff0901000001ull >> sh) & lv, c1 = (int)(int8_t)(0xff09f7ff0001ff00ull >> sh) & lv, K = (int)(int8_t)(0x0200140200000200ull >> sh) & lv;
+        const int c0 = (int)(int8_t)(W12_ROW_C0 >> sh) & lv, c1 = (int)(int8_t)(W12_ROW_C1 >> sh) & lv, K = (int)(int8_t)(W12_ROW_K >> sh) & lv;
         L = w12_load(&w12_comp(A[iw], h)).v;
         const Fq2S bj = w12_load(&B[jb]);
         Rv = lin2(bj.c0.v, c0, bj.c1.v, c1, K);

@@ -9,7 +9,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name", ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan"])
+@pytest.mark.parametrize("name", ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges"])
 def test_host_cpp(name, tmp_path):
     src = os.path.join(ROOT, "tests", "cpp", name + ".cc")
     if not os.path.exists(src):
@@ -20,7 +20,7 @@ def test_host_cpp(name, tmp_path):
     assert r.returncode == 0 and "PASS" in r.stdout, r.stdout[-2000:]
 
 
-@pytest.mark.parametrize("name", ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core"])
+@pytest.mark.parametrize("name", ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core", "test_w12_edges"])
 def test_host_cpp_with_the_column_wise_products(name, tmp_path):
     """-DLSA_FP29_COLS / -DLSA_F29_COLS / -DLSA_FR29_COLS select the column-wise forms of the 29-bit-limb products (17
     independent column accumulators instead of one serial multiply-add chain: fs29.h f29_dot_cols, fp29.h redc_cols,
@@ -66,10 +66,10 @@ def test_host_64_bit_limbs_agree_with_the_device_limbs(tmp_path):
 # an out-of-range index into a limb array) is undefined in the kernels too, where nothing reports it.  Pure host code
 # only: the two programs that link the HIP library (test_shim_io.cc, test_shim_domains.cc) stay out of this tier.
 SANITIZE = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan"]
+_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges"]
 _COLS = ["-DLSA_FP29_COLS", "-DLSA_F29_COLS", "-DLSA_FR29_COLS"]
 SANITIZED_PROGRAMS = ([(n, n, []) for n in _HEADER_TESTS]
-                      + [(n + "_cols", n, _COLS) for n in ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core"]]
+                      + [(n + "_cols", n, _COLS) for n in ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core", "test_w12_edges"]]
                       + [(n + "_32", n, ["-DLSA_FP_HOST32"]) for n in ["test_fp29", "test_glv", "test_tower29"]]
                       + [("test_fp_host_64", "test_fp_host", []), ("test_fp_host_32", "test_fp_host", ["-DLSA_FP_HOST32"])])
 
