@@ -519,6 +519,43 @@ int lsa_pairing_product_segments(const void *g1_jac, const void *g2_jac, const u
 int lsa_g1_normalize(const void *in_jac, size_t n, void *out_jac);
 int lsa_g2_normalize(const void *in_jac, size_t n, void *out_jac);
 
+/* ---- loading and writing keys ---------------------------------------------------------- */
+/* Batch forms of what libff's operator>> / operator<< do per point (compressed format: is_zero, X, one bit of Y), plus the
+ * checks they leave out: the range of the words, the curve equation of uncompressed points, membership in G2.
+ *
+ * Layouts.  x_mont: libff words of X, Montgomery form (32 B for G1, 64 B = c0, c1 for G2).  flags: one byte per point, bit 0 =
+ * libff's Y_lsb (the parity of the canonical Y; of Y.c0 for G2), bit 1 = is_zero.  Points are libff Jacobian (96 B / 192 B).
+ * status: one byte per point, below; a call returns LSA_OK whatever the statuses are.  Precedence: MALFORMED before NOT_ON_CURVE
+ * before NOT_IN_SUBGROUP. */
+#define LSA_PT_OK              0
+#define LSA_PT_INFINITY        1   /* accepted: the flag says zero / Z == 0 */
+#define LSA_PT_MALFORMED       2   /* a coordinate's words spell a value >= p, or a flag byte has a bit other than 0, 1 set */
+#define LSA_PT_NOT_ON_CURVE    3
+#define LSA_PT_NOT_IN_SUBGROUP 4   /* G2 only */
+/* out_jac[i] = (X, Y, one), Y the root of X^3 + b whose parity equals bit 0 -- the point libff's operator>> returns.  (G2: a
+ * root with c0 == 0 exists only when X^3 + b' lies in Fq and is a non-residue there; both roots then have parity 0, and the result
+ * is (0, r2) for bit 0 == 0 and (0, p - r2) for bit 0 == 1, r2 = (-rhs.c0)^((p+1)/4); libff accepts that mismatch silently, so
+ * does this call.)  With is_zero set X is ignored, as libff ignores it: (0, 1, 0), LSA_PT_INFINITY.  A point with status >= 2 is
+ * written as (0, 1, 0): a caller who ignores the status never feeds an off-curve point to an MSM.  check_subgroup != 0 (G2):
+ * points on the twist are tested with psi(P) == [6u^2]P, which holds exactly on G2 (csrc/fq_sqrt.h) -- 127 doublings and 39
+ * additions per point, in a kernel of its own.
+ * n_rejected: a HOST pointer, may be NULL; receives the number of statuses >= 2.  on_device != 0: every other pointer is a device
+ * pointer, and with n_rejected == NULL the call is asynchronous on lsa_stream(); with n_rejected it blocks.  Host mode blocks.
+ * LSA_ERR_INVALID, before any device work: a null pointer with n > 0, an output that overlaps an input (or the other output), a
+ * byte count that overflows size_t.  n == 0 is LSA_OK (*n_rejected = 0). */
+int lsa_g1_decompress(const void *x_mont, const uint8_t *flags, size_t n, void *out_jac, uint8_t *status, uint64_t *n_rejected, int on_device);
+int lsa_g2_decompress(const void *x_mont, const uint8_t *flags, size_t n, int check_subgroup, void *out_jac, uint8_t *status, uint64_t *n_rejected, int on_device);
+/* The checks alone, on Jacobian points (any Z; what arrives under NO_PT_COMPRESSION): words >= p in any coordinate give
+ * LSA_PT_MALFORMED, then Z == 0 gives LSA_PT_INFINITY, any other point is tested with Y^2 = X^3 + b Z^6 and, for G2 when asked
+ * for, the subgroup test.  The points are not modified.  Modes and refusals as above. */
+int lsa_g1_validate(const void *pts_jac, size_t n, uint8_t *status, uint64_t *n_rejected, int on_device);
+int lsa_g2_validate(const void *pts_jac, size_t n, int check_subgroup, uint8_t *status, uint64_t *n_rejected, int on_device);
+/* Jacobian -> compressed form, VALID points assumed: x_mont[i] = the canonical affine X in Montgomery words, flags as above.
+ * Infinity: X = 0 and flags = 3 (libff prints its zero() = (0, 1, 0): is_zero set, and Y = 1 is odd).  One batch inversion per
+ * eight points.  on_device != 0: device pointers, asynchronous on lsa_stream().  Refusals as above. */
+int lsa_g1_compress(const void *pts_jac, size_t n, void *x_mont, uint8_t *flags, int on_device);
+int lsa_g2_compress(const void *pts_jac, size_t n, void *x_mont, uint8_t *flags, int on_device);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

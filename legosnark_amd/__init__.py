@@ -106,6 +106,12 @@ def lib():
         L.lsa_fr_hadamard_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_lagrange.argtypes = [C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.lsa_g1_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.lsa_g2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.lsa_g1_validate.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.lsa_g2_validate.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        for name in ("lsa_g1_compress", "lsa_g2_compress"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_matvec.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.lsa_fr_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]
         L.lsa_fr_matrix_param.argtypes = [C.c_int]
@@ -466,6 +472,113 @@ def normalize(group, pts):
     fn = lib().lsa_g1_normalize if group == "g1" else lib().lsa_g2_normalize
     _check(fn(_host_ptr(pts), len(pts), _host_ptr(out)))
     return out
+
+
+# status bytes of decompress / validate_points (LSA_PT_*)
+PT_OK, PT_INFINITY, PT_MALFORMED, PT_NOT_ON_CURVE, PT_NOT_IN_SUBGROUP = range(5)
+
+
+def _point_rows(x, row_bytes):
+    """Rows of a point operand: a numpy array is made contiguous uint64 of row_bytes / 8 columns; a device tensor is counted."""
+    if isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, row_bytes // 8)
+        return x, len(x)
+    nbytes = x.numel() * x.element_size()
+    if nbytes % row_bytes:
+        raise ValueError("operand of %d bytes is not a whole number of %d-byte elements" % (nbytes, row_bytes))
+    return x, nbytes // row_bytes
+
+
+def _point_flags(flags, n, host):
+    if isinstance(flags, np.ndarray) != host:
+        raise ValueError("operands must be all numpy arrays or all torch CUDA tensors")
+    if host:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        nf = len(flags)
+    else:
+        if flags.element_size() != 1:
+            raise ValueError("flags: one byte per point (torch.uint8)")
+        nf = flags.numel()
+    if nf != n:
+        raise ValueError("%d flag bytes for %d points" % (nf, n))
+    return flags
+
+
+def decompress(group, x, flags, check_subgroup=True, out=None):
+    """libff's compressed points -> (points, status): x holds the X coordinates (Montgomery words, (n, 4) uint64 for "g1",
+    (n, 8) for "g2"), flags one byte per point (bit 0: parity of Y / Y.c0, bit 1: is_zero).  points: (n, 12) / (n, 24)
+    Jacobian with Z = one; status: PT_* per point, and every point with status >= PT_MALFORMED is (0, 1, 0).  check_subgroup
+    ("g2" only): points of the twist outside G2 get PT_NOT_IN_SUBGROUP.  numpy in -> numpy out; torch CUDA tensors in -> torch
+    CUDA tensors (`out` for the points, or new), asynchronous on the library's stream, ordered after torch's current stream."""
+    w = _group_width(group)
+    host = isinstance(x, np.ndarray)
+    x, n = _point_rows(x, w // 3 * 8)
+    flags = _point_flags(flags, n, host)
+
+    def call(px, pf, po, ps, dev):
+        if group == "g1":
+            _check(lib().lsa_g1_decompress(px, pf, n, po, ps, None, dev))
+        else:
+            _check(lib().lsa_g2_decompress(px, pf, n, 1 if check_subgroup else 0, po, ps, None, dev))
+    if host:
+        if out is not None:
+            raise ValueError("decompress: out is for torch CUDA tensors (numpy in gives new numpy arrays)")
+        pts = np.zeros((n, w), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint8)
+        call(_host_ptr(x), _host_ptr(flags), _host_ptr(pts), _host_ptr(status), 0)
+        return pts, status
+    import torch
+    if out is None:
+        out = torch.empty((n, w), dtype=torch.int64, device=x.device)
+    elif out.numel() * out.element_size() != n * w * 8:
+        raise ValueError("decompress: out holds %d bytes, %d points need %d" % (out.numel() * out.element_size(), n, n * w * 8))
+    status = torch.empty(n, dtype=torch.uint8, device=x.device)
+    _after_torch(x, flags, out)
+    call(_ptr(x), _ptr(flags), _ptr(out), _ptr(status), 1)
+    return out, status
+
+
+def validate_points(group, pts, check_subgroup=True):
+    """status (PT_* per point) of Jacobian points, any Z: words >= p, Z == 0, the curve equation and, for "g2" when asked for,
+    membership in G2.  numpy in -> numpy out; a torch CUDA tensor in -> a torch CUDA tensor, asynchronous on the library's stream."""
+    w = _group_width(group)
+    host = isinstance(pts, np.ndarray)
+    pts, n = _point_rows(pts, w * 8)
+
+    def call(pp, ps, dev):
+        if group == "g1":
+            _check(lib().lsa_g1_validate(pp, n, ps, None, dev))
+        else:
+            _check(lib().lsa_g2_validate(pp, n, 1 if check_subgroup else 0, ps, None, dev))
+    if host:
+        status = np.zeros(n, dtype=np.uint8)
+        call(_host_ptr(pts), _host_ptr(status), 0)
+        return status
+    import torch
+    status = torch.empty(n, dtype=torch.uint8, device=pts.device)
+    _after_torch(pts)
+    call(_ptr(pts), _ptr(status), 1)
+    return status
+
+
+def compress(group, pts):
+    """Valid Jacobian points -> (x, flags) in the layout decompress reads; infinity gives x = 0, flags = 3.  numpy in -> numpy
+    out; a torch CUDA tensor in -> torch CUDA tensors, asynchronous on the library's stream."""
+    w = _group_width(group)
+    host = isinstance(pts, np.ndarray)
+    pts, n = _point_rows(pts, w * 8)
+    fn = lib().lsa_g1_compress if group == "g1" else lib().lsa_g2_compress
+    if host:
+        x = np.zeros((n, w // 3), dtype=np.uint64)
+        flags = np.zeros(n, dtype=np.uint8)
+        _check(fn(_host_ptr(pts), n, _host_ptr(x), _host_ptr(flags), 0))
+        return x, flags
+    import torch
+    x = torch.empty((n, w // 3), dtype=torch.int64, device=pts.device)
+    flags = torch.empty(n, dtype=torch.uint8, device=pts.device)
+    _after_torch(pts)
+    _check(fn(_ptr(pts), n, _ptr(x), _ptr(flags), 1))
+    return x, flags
 
 
 def batch_exp(group, base, scalars, out=None):

@@ -731,6 +731,7 @@ public:
     // libff's), and testing every point that arrives as bytes would cost a key file of 2^20 points minutes.  So: once a
     // process has READ a G2 point, its host products on G2 bases other than the generator take the window ladder (275 us
     // instead of 76) for the rest of its life -- none of the reference's programs reads one; a verifier that does is correct.
+    // (lsa_load_points further down tests a whole vector on the device in one call and, when every point passed, leaves the flag alone.)
     static std::atomic<bool> &external_point_seen() { static std::atomic<bool> f{false}; return f; }
     static void note_external_point(const G_shim &p) {
         if constexpr (GROUP == 2) { if (!p.is_zero()) external_point_seen().store(true, std::memory_order_relaxed); }
@@ -1217,6 +1218,126 @@ void batch_to_special(std::vector<T> &vec) {
 }
 template <typename T>
 void batch_to_special_all_non_zeros(std::vector<T> &vec) { batch_to_special(vec); }
+
+// ---------------------------------------------------------------- key files: vectors of points in one library call
+// The reference streams a key with cputil::dumpIntoFile / loadFromFile (src/utils/util.h:56-96): a size line, then one
+// element per line through operator<< / operator>> -- one a^((p+1)/4) per G1 point and up to three per G2 point on one host
+// core when reading, one inversion per point when writing, and no test that a G2 point lies in G2.  These two keep the file
+// format (under the same NO_PT_COMPRESSION / BINARY_OUTPUT / MONTGOMERY_OUTPUT macros) and hand the arithmetic to the
+// device: the fields are parsed with the same FieldIO operators, then ONE lsa_gN_decompress (lsa_gN_validate under
+// NO_PT_COMPRESSION) covers the whole vector -- range of the words, the curve equation, and with check_subgroup the G2
+// subgroup test.  A rejected point throws std::runtime_error naming its index and status.  A G2 vector that passed with
+// check_subgroup does NOT set external_point_seen(): every point is proven to lie in G2, which is what that flag guards;
+// without the check it is set as operator>> sets it.  Stricter than operator>> in one respect: an is_zero or Y_lsb field
+// other than 0 / 1 is refused (operator>> takes any non-zero is_zero for infinity).
+// BINARY_OUTPUT: the per-element loop of the reference cannot read back what it wrote (a binary read takes the "\n" after
+// the size and after each element for data); lsa_load_points consumes exactly those bytes, so it reads what
+// lsa_dump_points -- and the reference's dump loop -- writes.
+namespace detail {
+inline const char *point_status_name(unsigned s) {
+    static const char *const names[] = {"OK", "INFINITY", "MALFORMED", "NOT_ON_CURVE", "NOT_IN_SUBGROUP"};
+    return s < 5 ? names[s] : "?";
+}
+inline void throw_rejected(const char *who, const std::vector<uint8_t> &status) {
+    for (size_t i = 0; i < status.size(); i++)
+        if (status[i] >= LSA_PT_MALFORMED)
+            throw std::runtime_error(std::string(who) + ": point " + std::to_string(i) + " rejected: " + point_status_name(status[i]) + " (status " +
+                                     std::to_string((unsigned)status[i]) + ")");
+}
+}  // namespace detail
+
+template <typename G>
+void lsa_load_points(std::istream &is, std::vector<G> &v, bool check_subgroup = true) {
+    constexpr int GROUP = detail::group_id<G>::value;
+    using FieldIO = typename G::FieldIO;
+    using F = decltype(G().X);
+    size_t n = 0;
+    is >> n;
+    if (!is) throw std::runtime_error("lsa_load_points: no size line");
+#ifdef BINARY_OUTPUT
+    consume_newline(is);
+#endif
+    v.assign(n, G::zero());
+    std::vector<uint8_t> status(n);
+    uint64_t rejected = 0;
+#ifdef NO_PT_COMPRESSION
+    for (size_t i = 0; i < n; i++) {
+        char is_zero = 0;
+        FieldIO tX, tY;
+        is >> is_zero >> tX >> tY;
+#ifdef BINARY_OUTPUT
+        consume_newline(is);
+#endif
+        if (!is) throw std::runtime_error("lsa_load_points: the stream ends or fails at point " + std::to_string(i));
+        if (is_zero != '0' && is_zero != '1') throw std::runtime_error("lsa_load_points: point " + std::to_string(i) + " rejected: MALFORMED (is_zero field)");
+        if (is_zero == '0') v[i] = G(tX.v, tY.v, F::one());
+    }
+    if (n) {
+        lsa_shim::GpuLock lock;
+        if (GROUP == 1) lsa_require(lsa_g1_validate(v.data(), n, status.data(), &rejected, 0), "lsa_load_points<G1>");
+        else lsa_require(lsa_g2_validate(v.data(), n, check_subgroup ? 1 : 0, status.data(), &rejected, 0), "lsa_load_points<G2>");
+    }
+#else
+    std::vector<F> xs(n);
+    std::vector<uint8_t> flags(n);
+    for (size_t i = 0; i < n; i++) {
+        char is_zero = 0;
+        unsigned char y_lsb = 0;
+        FieldIO tX;
+#ifndef BINARY_OUTPUT
+        is >> std::ws;
+#endif
+        is.read(&is_zero, 1);
+        consume_OUTPUT_SEPARATOR(is);
+        is >> tX;
+        consume_OUTPUT_SEPARATOR(is);
+        is.read(reinterpret_cast<char *>(&y_lsb), 1);
+#ifdef BINARY_OUTPUT
+        consume_newline(is);
+#endif
+        if (!is) throw std::runtime_error("lsa_load_points: the stream ends or fails at point " + std::to_string(i));
+        xs[i] = tX.v;
+        const bool fields_ok = (is_zero == '0' || is_zero == '1') && (y_lsb == '0' || y_lsb == '1');
+        flags[i] = fields_ok ? (uint8_t)(((is_zero - '0') << 1) | (y_lsb - '0')) : (uint8_t)4;     // 4: a bit no flag may carry -> MALFORMED
+    }
+    if (n) {
+        lsa_shim::GpuLock lock;
+        if (GROUP == 1) lsa_require(lsa_g1_decompress(xs.data(), flags.data(), n, v.data(), status.data(), &rejected, 0), "lsa_load_points<G1>");
+        else lsa_require(lsa_g2_decompress(xs.data(), flags.data(), n, check_subgroup ? 1 : 0, v.data(), status.data(), &rejected, 0), "lsa_load_points<G2>");
+    }
+#endif
+    if (rejected) detail::throw_rejected("lsa_load_points", status);
+    if (GROUP == 2 && !check_subgroup)
+        for (const G &p : v) G::note_external_point(p);
+}
+
+template <typename G>
+void lsa_dump_points(std::ostream &os, const std::vector<G> &v) {
+    constexpr int GROUP = detail::group_id<G>::value;
+    using FieldIO = typename G::FieldIO;
+    using F = decltype(G().X);
+    const size_t n = v.size();
+    os << n << "\n";
+    if (!n) return;
+#ifdef NO_PT_COMPRESSION
+    std::vector<G> a(n);
+    {
+        lsa_shim::GpuLock lock;
+        if (GROUP == 1) lsa_require(lsa_g1_normalize(v.data(), n, a.data()), "lsa_dump_points<G1>");
+        else lsa_require(lsa_g2_normalize(v.data(), n, a.data()), "lsa_dump_points<G2>");
+    }
+    for (const G &p : a) os << (p.is_zero() ? 1 : 0) << LSA_OUTPUT_SEPARATOR << FieldIO(p.X) << LSA_OUTPUT_SEPARATOR << FieldIO(p.Y) << "\n";
+#else
+    std::vector<F> xs(n);
+    std::vector<uint8_t> flags(n);
+    {
+        lsa_shim::GpuLock lock;
+        if (GROUP == 1) lsa_require(lsa_g1_compress(v.data(), n, xs.data(), flags.data(), 0), "lsa_dump_points<G1>");
+        else lsa_require(lsa_g2_compress(v.data(), n, xs.data(), flags.data(), 0), "lsa_dump_points<G2>");
+    }
+    for (size_t i = 0; i < n; i++) os << (int)((flags[i] >> 1) & 1) << LSA_OUTPUT_SEPARATOR << FieldIO(xs[i]) << LSA_OUTPUT_SEPARATOR << (unsigned)(flags[i] & 1) << "\n";
+#endif
+}
 
 }  // namespace libff
 
