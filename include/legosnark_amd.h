@@ -245,6 +245,23 @@ int lsa_g1_scalar_mul_batch(const void *pts_jac, const void *scalars_mont, size_
  * column).  Host pointers.  Row indices >= nrows are rejected (LSA_ERR_INVALID). */
 int lsa_g1_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols,
                              const void *exps_mont, size_t nrows, void *out_jac);
+/* The same two calls on G2 (the kc halves of Comm{c, kc}: Comm::operator*, src/prototools/commit.h:25-53; evalAsPolyOn over
+ * commitments, src/prototools/polytools.h:104-113): points are 192 B libff G2; argument checks, error codes, n == 0 / ncols == 0,
+ * host / device modes and blocking behaviour are those of the G1 calls.  What is new for G2: the result is the INTEGER
+ * multiple of the point by the canonical value of the scalar (0 <= s < r) for ANY point of the twist, in or out of the
+ * order-r subgroup -- no endomorphism is used (csrc/smul_g2.h).  The input is not checked for being on the curve;
+ * lsa_g2_validate does that. */
+int lsa_g2_scalar_mul_batch(const void *pts_jac, const void *scalars_mont, size_t n, void *out_jac, int on_device);
+int lsa_g2_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols,
+                             const void *exps_mont, size_t nrows, void *out_jac);
+/* Test and tool support, not needed to use the calls above: the compiled shape of the two ladders, so that tests and
+ * benchmarks follow a retune.  0 for an unknown selector. */
+#define LSA_SMUL_PARAM_G1_WINDOW_BITS 0     /* -> bits per signed digit, G1 */
+#define LSA_SMUL_PARAM_G2_WINDOW_BITS 1     /* -> bits per signed digit, G2 */
+#define LSA_SMUL_PARAM_G1_RESIDENT_ITEMS 2  /* -> items in flight in one pass of the persistent grid, G1 */
+#define LSA_SMUL_PARAM_G2_RESIDENT_ITEMS 3  /* -> the same, G2 */
+#define LSA_SMUL_PARAM_G2_LANES_PER_ITEM 4  /* -> lanes that share one G2 item */
+size_t lsa_smul_param(int which);
 
 /* ---- Fr vectors around the MSMs --------------------------------------------------------- */
 /* Witness coefficients of CPPoly::prove (src/gadgets/poly.h:55-67): with v of length 2^d and the

@@ -96,8 +96,12 @@ def lib():
         for name in ("lsa_g1_sum_on", "lsa_g2_sum_on"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.lsa_stream_join_to.argtypes = [C.c_void_p]
-        L.lsa_g1_scalar_mul_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
-        L.lsa_g1_sparse_matrix_msm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        for name in ("lsa_g1_scalar_mul_batch", "lsa_g2_scalar_mul_batch"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+        for name in ("lsa_g1_sparse_matrix_msm", "lsa_g2_sparse_matrix_msm"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.lsa_smul_param.argtypes = [C.c_int]
+        L.lsa_smul_param.restype = C.c_size_t
         L.lsa_fr_cppoly_witness.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_eval_mle.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_fold.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
@@ -604,39 +608,53 @@ def batch_exp(group, base, scalars, out=None):
     return out
 
 
-def scalar_mul_batch(pts, scalars, out=None):
-    """out[i] = scalars[i] * pts[i] on G1 (variable base).  numpy in -> numpy out (host);
-    torch CUDA tensors in -> torch CUDA tensor out (device)."""
+def scalar_mul_batch(pts, scalars, out=None, group="g1"):
+    """out[i] = scalars[i] * pts[i] (variable base) on G1 or, with group="g2", on G2 (24 words per point; the integer
+    multiple for any point of the twist).  numpy in -> numpy out (host); torch CUDA tensors in -> torch CUDA tensor out
+    (device)."""
+    w = _group_width(group)
+    fn = lib().lsa_g1_scalar_mul_batch if group == "g1" else lib().lsa_g2_scalar_mul_batch
     if isinstance(pts, np.ndarray):
-        pts = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, 12)
+        pts = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, w)
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
         if len(pts) != len(scalars):
             raise ValueError("need as many scalars as points")
         out = np.zeros_like(pts)
-        _check(lib().lsa_g1_scalar_mul_batch(_host_ptr(pts), _host_ptr(scalars), len(pts), _host_ptr(out), 0))
+        _check(fn(_host_ptr(pts), _host_ptr(scalars), len(pts), _host_ptr(out), 0))
         return out
-    n = pts.numel() * pts.element_size() // 96
+    n = pts.numel() * pts.element_size() // (8 * w)
     if out is None:
         import torch
-        out = torch.empty((n, 12), dtype=torch.int64, device=pts.device)
+        out = torch.empty((n, w), dtype=torch.int64, device=pts.device)
     _after_torch(pts, scalars, out)
-    _check(lib().lsa_g1_scalar_mul_batch(_ptr(pts), _ptr(scalars), n, _ptr(out), 1))
+    _check(fn(_ptr(pts), _ptr(scalars), n, _ptr(out), 1))
     return out
 
 
-def sparse_matrix_msm(vals, rows, col_ptr, exps):
-    """mtxmultiexp on a CSC matrix of G1 elements: out[j] = sum_e exps[rows[e]] * vals[e]."""
-    vals = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, 12)
+def sparse_matrix_msm(vals, rows, col_ptr, exps, group="g1"):
+    """mtxmultiexp on a CSC matrix of G1 (or, with group="g2", G2) elements: out[j] = sum_e exps[rows[e]] * vals[e]."""
+    w = _group_width(group)
+    fn = lib().lsa_g1_sparse_matrix_msm if group == "g1" else lib().lsa_g2_sparse_matrix_msm
+    vals = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, w)
     rows = np.ascontiguousarray(rows, dtype=np.uint32)
     col_ptr = np.ascontiguousarray(col_ptr, dtype=np.uint64)
     exps = np.ascontiguousarray(exps, dtype=np.uint64).reshape(-1, 4)
     ncols = len(col_ptr) - 1
     if ncols < 0 or len(vals) != len(rows) or (ncols >= 0 and int(col_ptr[-1]) != len(vals)):
         raise ValueError("inconsistent CSC arrays")
-    out = np.zeros((ncols, 12), dtype=np.uint64)
-    _check(lib().lsa_g1_sparse_matrix_msm(_host_ptr(vals), _host_ptr(rows), _host_ptr(col_ptr), ncols,
-                                          _host_ptr(exps), len(exps), _host_ptr(out)))
+    out = np.zeros((ncols, w), dtype=np.uint64)
+    _check(fn(_host_ptr(vals), _host_ptr(rows), _host_ptr(col_ptr), ncols, _host_ptr(exps), len(exps), _host_ptr(out)))
     return out
+
+
+SMUL_PARAMS = ("g1_window_bits", "g2_window_bits", "g1_resident_items", "g2_resident_items", "g2_lanes_per_item")
+
+
+def smul_param(which):
+    """The compiled shape of the variable-base ladders (lsa_smul_param): `which` is a selector number or one of SMUL_PARAMS."""
+    if isinstance(which, str):
+        which = SMUL_PARAMS.index(which)
+    return int(lib().lsa_smul_param(int(which)))
 
 
 def _log2_exact(n):

@@ -1597,31 +1597,39 @@ struct DevBuf {
 }  // namespace
 
 // ---------------------------------------------------------------- variable-base scalar mul / sparse matrix
-extern "C" {
-int lsa_g1_scalar_mul_batch(const void *pts_jac, const void *scalars, size_t n, void *out_jac, int on_device) {
-    LSA_TRACE_CALL("g1_scalar_mul_batch", n);
+namespace {
+inline int smul_device(const Jac<Fq> *p, const Fr *s, const uint32_t *idx, size_t n, Jac<Fq> *o, hipStream_t st) { return g1_scalar_mul_device(p, s, idx, n, o, st); }
+inline int smul_device(const Jac<Fq2> *p, const Fr *s, const uint32_t *idx, size_t n, Jac<Fq2> *o, hipStream_t st) { return g2_scalar_mul_device(p, s, idx, n, o, st); }
+inline int colsum_device(const Jac<Fq> *it, const uint64_t *cp, size_t ncols, Jac<Fq> *o, hipStream_t st) { return g1_column_sums_device(it, cp, ncols, o, st); }
+inline int colsum_device(const Jac<Fq2> *it, const uint64_t *cp, size_t ncols, Jac<Fq2> *o, hipStream_t st) { return g2_column_sums_device(it, cp, ncols, o, st); }
+
+// the body of lsa_g1_scalar_mul_batch / lsa_g2_scalar_mul_batch (F = Fq / Fq2)
+template <class F>
+int scalar_mul_batch(const void *pts_jac, const void *scalars, size_t n, void *out_jac, int on_device) {
     int rc = require_ready();
     if (rc) return rc;
     if (n == 0) return LSA_OK;
     if (!pts_jac || !scalars || !out_jac) { set_error("scalar_mul_batch: null argument"); return LSA_ERR_INVALID; }
     rc = msm_join(g.stream);
     if (rc) return rc;
-    if (on_device) return g1_scalar_mul_device((const Jac<Fq> *)pts_jac, (const Fr *)scalars, nullptr, n, (Jac<Fq> *)out_jac, g.stream);
+    if (on_device) return smul_device((const Jac<F> *)pts_jac, (const Fr *)scalars, nullptr, n, (Jac<F> *)out_jac, g.stream);
     DevBuf d_p, d_s, d_o;
-    if (d_p.alloc(n * sizeof(Jac<Fq>)) || d_s.alloc(n * sizeof(Fr)) || d_o.alloc(n * sizeof(Jac<Fq>))) {
+    if (d_p.alloc(n * sizeof(Jac<F>)) || d_s.alloc(n * sizeof(Fr)) || d_o.alloc(n * sizeof(Jac<F>))) {
         set_error("scalar_mul_batch: hipMalloc failed");
         return LSA_ERR_NOMEM;
     }
-    LSA_UPLOAD(d_p.p, pts_jac, n * sizeof(Jac<Fq>));
+    LSA_UPLOAD(d_p.p, pts_jac, n * sizeof(Jac<F>));
     LSA_UPLOAD(d_s.p, scalars, n * sizeof(Fr));
-    rc = g1_scalar_mul_device((const Jac<Fq> *)d_p.p, (const Fr *)d_s.p, nullptr, n, (Jac<Fq> *)d_o.p, g.stream);
+    rc = smul_device((const Jac<F> *)d_p.p, (const Fr *)d_s.p, nullptr, n, (Jac<F> *)d_o.p, g.stream);
     if (rc) return rc;
-    LSA_DOWNLOAD(out_jac, d_o.p, n * sizeof(Jac<Fq>));
+    LSA_DOWNLOAD(out_jac, d_o.p, n * sizeof(Jac<F>));
     return LSA_OK;
 }
 
-int lsa_g1_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols,
-                             const void *exps, size_t nrows, void *out_jac) {
+// the body of lsa_g1_sparse_matrix_msm / lsa_g2_sparse_matrix_msm
+template <class F>
+int sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols, const void *exps, size_t nrows,
+                      void *out_jac) {
     int rc = require_ready();
     if (rc) return rc;
     if (ncols == 0) return LSA_OK;
@@ -1636,24 +1644,53 @@ int lsa_g1_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const u
     rc = msm_join(g.stream);
     if (rc) return rc;
     DevBuf d_v, d_r, d_c, d_e, d_items, d_o;
-    if (d_v.alloc(nnz * sizeof(Jac<Fq>)) || d_r.alloc(nnz * sizeof(uint32_t)) || d_c.alloc((ncols + 1) * sizeof(uint64_t)) ||
-        d_e.alloc(nrows * sizeof(Fr)) || d_items.alloc(nnz * sizeof(Jac<Fq>)) || d_o.alloc(ncols * sizeof(Jac<Fq>))) {
+    if (d_v.alloc(nnz * sizeof(Jac<F>)) || d_r.alloc(nnz * sizeof(uint32_t)) || d_c.alloc((ncols + 1) * sizeof(uint64_t)) ||
+        d_e.alloc(nrows * sizeof(Fr)) || d_items.alloc(nnz * sizeof(Jac<F>)) || d_o.alloc(ncols * sizeof(Jac<F>))) {
         set_error("sparse_matrix_msm: hipMalloc failed");
         return LSA_ERR_NOMEM;
     }
     if (nnz) {
-        LSA_UPLOAD(d_v.p, vals_jac, nnz * sizeof(Jac<Fq>));
+        LSA_UPLOAD(d_v.p, vals_jac, nnz * sizeof(Jac<F>));
         LSA_UPLOAD(d_r.p, rows, nnz * sizeof(uint32_t));
         LSA_UPLOAD(d_e.p, exps, nrows * sizeof(Fr));
     }
     LSA_UPLOAD(d_c.p, col_ptr, (ncols + 1) * sizeof(uint64_t));
-    rc = g1_scalar_mul_device((const Jac<Fq> *)d_v.p, (const Fr *)d_e.p, (const uint32_t *)d_r.p, nnz, (Jac<Fq> *)d_items.p, g.stream);
+    rc = smul_device((const Jac<F> *)d_v.p, (const Fr *)d_e.p, (const uint32_t *)d_r.p, nnz, (Jac<F> *)d_items.p, g.stream);
     if (rc) return rc;
-    rc = g1_column_sums_device((const Jac<Fq> *)d_items.p, (const uint64_t *)d_c.p, ncols, (Jac<Fq> *)d_o.p, g.stream);
+    rc = colsum_device((const Jac<F> *)d_items.p, (const uint64_t *)d_c.p, ncols, (Jac<F> *)d_o.p, g.stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(out_jac, d_o.p, ncols * sizeof(Jac<Fq>));
+    LSA_DOWNLOAD(out_jac, d_o.p, ncols * sizeof(Jac<F>));
     return LSA_OK;
+}
+}  // namespace
+
+extern "C" {
+int lsa_g1_scalar_mul_batch(const void *pts_jac, const void *scalars, size_t n, void *out_jac, int on_device) {
+    LSA_TRACE_CALL("g1_scalar_mul_batch", n);
+    return scalar_mul_batch<Fq>(pts_jac, scalars, n, out_jac, on_device);
+}
+int lsa_g2_scalar_mul_batch(const void *pts_jac, const void *scalars, size_t n, void *out_jac, int on_device) {
+    LSA_TRACE_CALL("g2_scalar_mul_batch", n);
+    return scalar_mul_batch<Fq2>(pts_jac, scalars, n, out_jac, on_device);
+}
+int lsa_g1_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols,
+                             const void *exps, size_t nrows, void *out_jac) {
+    return sparse_matrix_msm<Fq>(vals_jac, rows, col_ptr, ncols, exps, nrows, out_jac);
+}
+int lsa_g2_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols,
+                             const void *exps, size_t nrows, void *out_jac) {
+    return sparse_matrix_msm<Fq2>(vals_jac, rows, col_ptr, ncols, exps, nrows, out_jac);
+}
+size_t lsa_smul_param(int which) {
+    switch (which) {
+    case LSA_SMUL_PARAM_G1_WINDOW_BITS: return g1_smul_param(0);
+    case LSA_SMUL_PARAM_G2_WINDOW_BITS: return g2_smul_param(0);
+    case LSA_SMUL_PARAM_G1_RESIDENT_ITEMS: return g1_smul_param(1);
+    case LSA_SMUL_PARAM_G2_RESIDENT_ITEMS: return g2_smul_param(1);
+    case LSA_SMUL_PARAM_G2_LANES_PER_ITEM: return g2_smul_param(2);
+    }
+    return 0;
 }
 }  // extern "C"
 

@@ -67,6 +67,12 @@ void batch_exp_release();      // the grow-only table workspace (lsa_shutdown)
 // and per-column sums of a CSC-ordered item array.  Device pointers.
 int g1_scalar_mul_device(const Jac<Fq> *d_pts, const Fr *d_scalars, const uint32_t *d_sidx, size_t n, Jac<Fq> *d_out, hipStream_t st);
 int g1_column_sums_device(const Jac<Fq> *d_items, const uint64_t *d_col_ptr, size_t ncols, Jac<Fq> *d_out, hipStream_t st);
+// scalar_mul_g2.hip: the same on G2, same contract.  The product is the integer multiple for any point of the twist.
+int g2_scalar_mul_device(const Jac<Fq2> *d_pts, const Fr *d_scalars, const uint32_t *d_sidx, size_t n, Jac<Fq2> *d_out, hipStream_t st);
+int g2_column_sums_device(const Jac<Fq2> *d_items, const uint64_t *d_col_ptr, size_t ncols, Jac<Fq2> *d_out, hipStream_t st);
+// the compiled shape of the two ladders (lsa_smul_param): which = 0 window bits, 1 resident items, 2 lanes per item (G2 only)
+size_t g1_smul_param(int which);
+size_t g2_smul_param(int which);
 
 // fr_vec.hip: Fr streaming kernels (device pointers, asynchronous on st).
 int fr_cppoly_fold_device(const Fr *d_v, size_t d, const Fr *d_r, Fr *d_w, Fr *d_tmp, hipStream_t st);

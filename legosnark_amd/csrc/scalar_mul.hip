@@ -93,4 +93,7 @@ int g1_column_sums_device(const Jac<Fq> *d_items, const uint64_t *d_col_ptr, siz
     return LSA_OK;
 }
 
+// lsa_smul_param: 0 = window width in bits (SMUL_TBL = 2^(w-1) table entries), 1 = items resident in one pass of the persistent grid
+size_t g1_smul_param(int which) { return which == 0 ? (size_t)4 : which == 1 ? (size_t)SMUL_BLOCKS * 256 : 0; }
+
 }  // namespace lsa

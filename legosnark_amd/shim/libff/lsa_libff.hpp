@@ -1099,9 +1099,25 @@ T multi_exp_with_mixed_addition(typename std::vector<T>::const_iterator vec_star
 //   out[j] = sum over (val, pos) in m[j] of exps[pos] * val.
 // Flattens the columns to CSC arrays and forwards to lsa_g1_sparse_matrix_msm (one batched
 // scalar-multiplication kernel + one per-column sum instead of |m| sparsemexpG calls).
-template <class Col, class FieldT>
-void lsa_mtxmultiexp(std::vector<alt_bn128_G1> &out, const std::vector<FieldT> &exps, const std::vector<Col> &m) {
-    std::vector<alt_bn128_G1> vals;
+// The same for columns of CoeffPos<alt_bn128_G2> (the kc halves of commitments): lsa_g2_sparse_matrix_msm.
+namespace detail {
+inline int sparse_matrix_msm(const alt_bn128_G1 *vals, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols, const void *exps,
+                             size_t nrows, alt_bn128_G1 *out) {
+    return lsa_g1_sparse_matrix_msm(vals, rows, col_ptr, ncols, exps, nrows, out);
+}
+inline int sparse_matrix_msm(const alt_bn128_G2 *vals, const uint32_t *rows, const uint64_t *col_ptr, size_t ncols, const void *exps,
+                             size_t nrows, alt_bn128_G2 *out) {
+    return lsa_g2_sparse_matrix_msm(vals, rows, col_ptr, ncols, exps, nrows, out);
+}
+inline int scalar_mul_batch(const alt_bn128_G1 *pts, const void *scalars, size_t n, alt_bn128_G1 *out) {
+    return lsa_g1_scalar_mul_batch(pts, scalars, n, out, 0);
+}
+inline int scalar_mul_batch(const alt_bn128_G2 *pts, const void *scalars, size_t n, alt_bn128_G2 *out) {
+    return lsa_g2_scalar_mul_batch(pts, scalars, n, out, 0);
+}
+template <class G, class Col, class FieldT>
+void mtxmultiexp(std::vector<G> &out, const std::vector<FieldT> &exps, const std::vector<Col> &m) {
+    std::vector<G> vals;
     std::vector<uint32_t> rows;
     std::vector<uint64_t> col_ptr(m.size() + 1, 0);
     size_t nnz = 0;
@@ -1115,20 +1131,37 @@ void lsa_mtxmultiexp(std::vector<alt_bn128_G1> &out, const std::vector<FieldT> &
         }
         col_ptr[j + 1] = vals.size();
     }
-    out.assign(m.size(), alt_bn128_G1::zero());
+    out.assign(m.size(), G::zero());
     lsa_shim::GpuLock lock;
     lsa_shim::StatScope scope(lsa_shim::ST_SPARSE_MSM, nnz);
-    lsa_require(lsa_g1_sparse_matrix_msm(vals.data(), rows.data(), col_ptr.data(), m.size(), exps.data(), exps.size(), out.data()),
-                "mtxmultiexp");
+    lsa_require(sparse_matrix_msm(vals.data(), rows.data(), col_ptr.data(), m.size(), exps.data(), exps.size(), out.data()), "mtxmultiexp");
 }
-// out[i] = scalars[i] * pts[i] (the loop of src/examples/cplink.cc:51-58 when the bases differ)
+template <class G, class FieldT>
+std::vector<G> scalar_mul_batch(const std::vector<G> &pts, const std::vector<FieldT> &scalars) {
+    const size_t n = pts.size() < scalars.size() ? pts.size() : scalars.size();
+    std::vector<G> out(n, G::zero());
+    lsa_shim::GpuLock lock;
+    lsa_require(scalar_mul_batch(pts.data(), scalars.data(), n, out.data()), "scalar_mul_batch");
+    return out;
+}
+}  // namespace detail
+template <class Col, class FieldT>
+void lsa_mtxmultiexp(std::vector<alt_bn128_G1> &out, const std::vector<FieldT> &exps, const std::vector<Col> &m) {
+    detail::mtxmultiexp(out, exps, m);
+}
+template <class Col, class FieldT>
+void lsa_mtxmultiexp(std::vector<alt_bn128_G2> &out, const std::vector<FieldT> &exps, const std::vector<Col> &m) {
+    detail::mtxmultiexp(out, exps, m);
+}
+// out[i] = scalars[i] * pts[i] (the loop of src/examples/cplink.cc:51-58 when the bases differ); on G2 the b * kc half of
+// Comm::operator* over a vector of commitments (src/prototools/commit.h:25-53), for points in or out of the subgroup
 template <class FieldT>
 std::vector<alt_bn128_G1> lsa_scalar_mul_batch(const std::vector<alt_bn128_G1> &pts, const std::vector<FieldT> &scalars) {
-    const size_t n = pts.size() < scalars.size() ? pts.size() : scalars.size();
-    std::vector<alt_bn128_G1> out(n, alt_bn128_G1::zero());
-    lsa_shim::GpuLock lock;
-    lsa_require(lsa_g1_scalar_mul_batch(pts.data(), scalars.data(), n, out.data(), 0), "scalar_mul_batch");
-    return out;
+    return detail::scalar_mul_batch(pts, scalars);
+}
+template <class FieldT>
+std::vector<alt_bn128_G2> lsa_scalar_mul_batch(const std::vector<alt_bn128_G2> &pts, const std::vector<FieldT> &scalars) {
+    return detail::scalar_mul_batch(pts, scalars);
 }
 
 // fixed-base tables.  libff: `template<typename T> using window_table = std::vector<std::vector<T>>` with
