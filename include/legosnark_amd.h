@@ -404,6 +404,63 @@ size_t lsa_fr_matrix_param(int which);
  * partial sums and the finishing kernel.  0 for arguments the call refuses. */
 size_t lsa_fr_matvec_slices(size_t rows, size_t cols, int side);
 
+/* ---- sparse Fr matrices resident on the device: R1CS products and the QAP witness map (src/examples/legogrothmatrix.cc) ---- */
+/* A sparse matrix over Fr kept on the device, made from host CSR arrays: vals_mont nnz x 32 bytes (libff Montgomery words; any
+ * 256-bit pattern counts as its value mod r), cols nnz column indices, row_ptr nrows + 1 offsets (row r is the entries
+ * row_ptr[r] .. row_ptr[r + 1] - 1).  Duplicate column indices inside a row are legal and summed (libsnark's linear combinations
+ * are not merged); empty rows are legal.  keep_transpose != 0 also keeps the transposed copy (built on the host by a counting
+ * sort), which side 0 of lsa_fr_sparse_matvec needs; it doubles the device memory of the handle.
+ * Every stored coefficient gets a class here: exactly the canonical words of +1 or of -1 (r - 1), or general.  Units cost a limb
+ * addition per entry instead of a product and their coefficient is never read (csrc/fr_sparse.h).
+ * The arrays are copied: the caller's may go after the call.  Blocking.  *out is null after any failure.
+ * LSA_ERR_INVALID, before any device work: row_ptr[0] != 0, a decreasing row_ptr, row_ptr[nrows] != nnz, a column index >= ncols,
+ * a null pointer with a non-empty extent (or a null out), nrows or ncols above 2^32 - 1.  Because every index is checked here, no
+ * kernel gathers out of bounds as long as x has the length the side says. */
+typedef struct lsa_fr_sparse lsa_fr_sparse;
+int lsa_fr_sparse_create(const void *vals_mont, const uint32_t *cols, const uint64_t *row_ptr, size_t nrows, size_t ncols, size_t nnz,
+                         int keep_transpose, lsa_fr_sparse **out);
+/* Waits for the library's stream (a product of the matrix may still be running), then frees the device copies.  Null: no-op. */
+void lsa_fr_sparse_destroy(lsa_fr_sparse *m);
+size_t lsa_fr_sparse_rows(const lsa_fr_sparse *m);
+size_t lsa_fr_sparse_cols(const lsa_fr_sparse *m);
+size_t lsa_fr_sparse_nnz(const lsa_fr_sparse *m);
+
+/* side 1: out[r] = sum_c M[r][c] x[c] (nrows results; x has ncols entries); side 0: out[c] = sum_r x[r] M[r][c] (ncols results; x
+ * has nrows entries; needs keep_transpose, else LSA_ERR_INVALID).  The sides are those of lsa_fr_matvec, and so are the bytes:
+ * canonical words, whatever the order of summation.  An empty row gives zero; a matrix without entries gives zeros without a
+ * launch over entries; no results is a successful no-op.
+ * Work is cut by nonzeros: rows of at most LSA_FR_SPARSE_PARAM_SHORT_MAX entries are one lane's each (of at most _LANE_MAX
+ * entries when the matrix has at least _LANE_FILL rows between the two: enough lanes for the whole device), longer rows are cut into
+ * chunks of LSA_FR_SPARSE_PARAM_CHUNK entries, a wavefront each, and a finishing kernel adds a row's partial sums (csrc/fr_sparse.hip).
+ * on_device != 0: x, out are device pointers (16-byte aligned) and the call is asynchronous on lsa_stream(), with no host
+ * synchronisation inside (the staging -- the chunks' partial sums, x and out for host callers -- is grow-only and owned by the
+ * library: only the first call of a larger size waits for the device).  Else host pointers and a blocking call.  x is not modified.
+ * LSA_ERR_INVALID, before any device work: a null matrix, side not 0 or 1, side 0 without the transpose, a null pointer with a
+ * non-empty extent, out overlapping x, a misaligned device pointer. */
+int lsa_fr_sparse_matvec(const lsa_fr_sparse *m, const void *x_mont, int side, void *out_mont, int on_device);
+
+/* H of the R1CS (A, B, C) at the assignment z (z[0] = 1): a = A z, b = B z, c = C z into library staging, then
+ * lsa_fr_hadamard_quotient on them: H Z = (a + d1 Z)(b + d2 Z) - (c + d3 Z), libsnark's r1cs_to_qap_witness_map; with zero d123
+ * Groth16's H.  n = the common row count <= m; big_log, small_log, omega, coset_g, d123, h_out (m + 1 Fr) and the refusals exactly
+ * as documented for lsa_fr_hadamard_quotient; d123 == NULL: zeros.  z: as many Fr as the matrices have columns.
+ * libsnark's extra input-consistency rows (one constraint 1 * z[i] = 0 appended to A per public input) need no special case:
+ * they are ordinary rows of A with one unit entry and empty rows of B and C.
+ * on_device != 0: z, h_out are device pointers (16-byte aligned), asynchronous on lsa_stream() as lsa_fr_hadamard_quotient is;
+ * h_out can go straight to lsa_msm_run_async as the scalar vector.  Else host pointers, blocking.
+ * LSA_ERR_INVALID also: a null matrix, differing row or column counts among A, B and C, more rows than the domain has points,
+ * h_out overlapping z, a misaligned device pointer. */
+int lsa_fr_qap_witness(const lsa_fr_sparse *A, const lsa_fr_sparse *B, const lsa_fr_sparse *C, const void *z_mont, size_t big_log,
+                       int small_log, const void *omega_mont, const void *coset_g_mont, const void *d123_mont, void *h_out_mont, int on_device);
+
+/* Test and tool support: the compiled shape of the sparse kernels, so that tests and benchmarks follow a retune.  0 for an
+ * unknown selector. */
+#define LSA_FR_SPARSE_PARAM_SHORT_MAX 0   /* -> entries up to which a row is summed by one lane */
+#define LSA_FR_SPARSE_PARAM_CHUNK 1       /* -> entries of a longer row per wavefront and partial sum */
+#define LSA_FR_SPARSE_PARAM_UNIT_MAX 2    /* -> +-1 terms the unit accumulator takes before it is joined (csrc/fr_sparse.h) */
+#define LSA_FR_SPARSE_PARAM_LANE_MAX 3    /* -> entries up to which a row is one lane's when the matrix has LANE_FILL rows of SHORT_MAX + 1 .. LANE_MAX entries */
+#define LSA_FR_SPARSE_PARAM_LANE_FILL 4   /* -> that number of rows */
+size_t lsa_fr_sparse_param(int which);
+
 /* ---- pairing ---------------------------------------------------------------------------- */
 /* out[i] = miller_loop(precompute_G1(P_i), precompute_G2(Q_i)), i < n: replaces libff
  * alt_bn128_pp::precompute_G1 / precompute_G2 / miller_loop (src/utils/globl.h:96-102,

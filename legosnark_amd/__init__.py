@@ -122,6 +122,17 @@ def lib():
         L.lsa_fr_matrix_param.restype = C.c_size_t
         L.lsa_fr_matvec_slices.argtypes = [C.c_size_t, C.c_size_t, C.c_int]
         L.lsa_fr_matvec_slices.restype = C.c_size_t
+        L.lsa_fr_sparse_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
+        L.lsa_fr_sparse_destroy.argtypes = [C.c_void_p]
+        L.lsa_fr_sparse_destroy.restype = None
+        for name in ("lsa_fr_sparse_rows", "lsa_fr_sparse_cols", "lsa_fr_sparse_nnz"):
+            getattr(L, name).argtypes = [C.c_void_p]
+            getattr(L, name).restype = C.c_size_t
+        L.lsa_fr_sparse_matvec.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.lsa_fr_qap_witness.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int]
+        L.lsa_fr_sparse_param.argtypes = [C.c_int]
+        L.lsa_fr_sparse_param.restype = C.c_size_t
         L.lsa_fr_sumcheck_round.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_scale_upper.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_eq_table.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int]
@@ -924,6 +935,80 @@ def fr_matmul(a, b, rows_a, inner, cols_b, out=None):
     b = _fr_matrix_operand("fr_matmul", b, inner * cols_b, "b")
     return _fr_matrix_call("fr_matmul", [a, b], rows_a * cols_b, out,
                            lambda p, o, dev: _check(lib().lsa_fr_matmul(p[0], p[1], rows_a, inner, cols_b, o, dev)))
+
+
+def fr_sparse_params():
+    """The compiled shape of the sparse Fr kernels (lsa_fr_sparse_param): the entries up to which a row is one lane's, the
+    entries of a longer row per wavefront and partial sum, the +-1 terms csrc/fr_sparse.h adds up before it joins them into
+    the running sum, and the longer limit for a lane (lane_max) that holds when a matrix has lane_fill rows of short_max + 1
+    .. lane_max entries."""
+    names = ("short_max", "chunk", "unit_max", "lane_max", "lane_fill")
+    return {name: int(lib().lsa_fr_sparse_param(i)) for i, name in enumerate(names)}
+
+
+class FrSparse:
+    """A sparse matrix over Fr resident on the device (lsa_fr_sparse_create), from host CSR arrays: vals (nnz, 4) uint64
+    Montgomery words, cols nnz uint32, row_ptr rows + 1 uint64; `ncols` columns.  keep_transpose keeps the transposed copy
+    that side 0 of matvec needs."""
+
+    def __init__(self, vals, cols, row_ptr, ncols, keep_transpose=True):
+        vals = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, 4)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64).reshape(-1)
+        if len(row_ptr) < 1:
+            raise ValueError("FrSparse: row_ptr has rows + 1 entries")
+        if len(vals) != len(cols):
+            raise ValueError("FrSparse: %d coefficients, %d column indices" % (len(vals), len(cols)))
+        self.handle = C.c_void_p()
+        _check(lib().lsa_fr_sparse_create(_host_ptr(vals), _host_ptr(cols), _host_ptr(row_ptr), len(row_ptr) - 1, int(ncols), len(vals),
+                                          1 if keep_transpose else 0, C.byref(self.handle)))
+
+    rows = property(lambda self: int(lib().lsa_fr_sparse_rows(self.handle)))
+    cols = property(lambda self: int(lib().lsa_fr_sparse_cols(self.handle)))
+    nnz = property(lambda self: int(lib().lsa_fr_sparse_nnz(self.handle)))
+
+    def matvec(self, x, side=1, out=None):
+        """side 1: out[r] = sum_c M[r][c] x[c]; side 0: out[c] = sum_r x[r] M[r][c] (the sides of fr_matvec).  numpy in -> a
+        new numpy array; a torch CUDA tensor in -> a torch CUDA tensor (`out`, or a new one), asynchronous on the library's
+        stream."""
+        side = int(side)
+        if side not in (0, 1):
+            raise ValueError("FrSparse.matvec: side %r (0: sums of rows weighted by x[r], 1: sums of columns weighted by x[c])" % side)
+        if not self.handle:
+            raise ValueError("FrSparse.matvec: the matrix is closed")
+        x = _fr_matrix_operand("FrSparse.matvec", x, self.cols if side else self.rows, "x")
+        return _fr_matrix_call("FrSparse.matvec", [x], self.rows if side else self.cols, out,
+                               lambda p, o, dev: _check(lib().lsa_fr_sparse_matvec(self.handle, p[0], side, o, dev)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().lsa_fr_sparse_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fr_qap_witness(A, B, C, z, big_log, small_log=None, omega=None, coset=None, d123=None, out=None):
+    """The witness map of a Groth16-style prover (lsa_fr_qap_witness): H with H Z = (A z + d1 Z)(B z + d2 Z) - (C z + d3 Z) for
+    the FrSparse matrices A, B, C of an R1CS and the assignment z, on the domain of fr_hadamard_quotient (big_log, small_log,
+    omega, coset as there); m + 1 coefficients.  d123 None: no blinding.  numpy z -> a new numpy array; a torch CUDA tensor ->
+    a torch CUDA tensor (`out`, or a new one), asynchronous on the library's stream."""
+    if omega is None or coset is None:
+        raise ValueError("fr_qap_witness: omega and coset are required")
+    omega = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+    cg = np.ascontiguousarray(coset, dtype=np.uint64).reshape(4)
+    d = None if d123 is None else np.ascontiguousarray(d123, dtype=np.uint64).reshape(3, 4)
+    dp = None if d is None else _host_ptr(d)
+    sl = -1 if small_log is None else int(small_log)
+    m = (1 << big_log) + ((1 << sl) if sl >= 0 else 0)
+    z = _fr_matrix_operand("fr_qap_witness", z, A.cols, "z")
+    return _fr_matrix_call("fr_qap_witness", [z], m + 1, out,
+                           lambda p, o, dev: _check(lib().lsa_fr_qap_witness(A.handle, B.handle, C.handle, p[0], big_log, sl, _host_ptr(omega),
+                                                                             _host_ptr(cg), dp, o, dev)))
 
 
 def sum_async(group, d_pts, n, d_out):

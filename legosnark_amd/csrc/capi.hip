@@ -731,6 +731,7 @@ static void release_stage_buffers() {
     pairing_release();
     fr_poly_release();
     fr_matrix_release();
+    fr_sparse_release();
     point_load_release();
 }
 

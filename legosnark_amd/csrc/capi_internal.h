@@ -49,6 +49,7 @@ void comm_release();               // comm.hip: called by lsa_shutdown
 void pairing_release();            // capi_pairing.hip: staging buffers and the G2 line-table cache
 void fr_poly_release();            // fr_poly.hip: staging buffers of the Lipmaa quotient and the Lagrange row
 void fr_matrix_release();          // fr_matrix.hip: staging buffers of the matrix product and the weighted row / column sums
+void fr_sparse_release();          // fr_sparse.hip: staging buffers of the sparse products and the witness map
 void point_load_release();         // point_load.hip: staging buffers of point decompression, validation and compression
 
 // grow-only device staging buffer of the host-buffer entry points (the libff shim calls them
