@@ -339,7 +339,8 @@ int lsa_fr_ntt_step(void *a_mont, size_t big_log, size_t small_log, const void *
  *           Z = x^m - 1;  otherwise libfqfft's step radix-2 domain, m = 2^big_log + 2^small_log, omega and the limits as
  *           for lsa_fr_ntt_step, Z = (x^(2^big_log) - 1)(x^(2^small_log) - omega^(2^small_log)).
  *   a, b, c: n <= m values each on the domain's points in the domain's order; entries n .. m-1 count as zero (the
- *           reference's zero-filled vectors).  Not modified.
+ *           reference's zero-filled vectors).  Not modified.  With n == 0 they are not read and may be null (an empty device
+ *           tensor has no address).
  *   d123:   HOST, three Fr: the commitment randomness d1, d2, d3 of a, b, c.
  *   coset_g: HOST, one Fr: the coset on which the division by Z happens (the reference: Fr::multiplicative_generator).  A
  *           coset on which Z may vanish is refused before any device work: coset_g^m = 1 on the basic domain,

@@ -519,29 +519,33 @@ def _point_flags(flags, n, host):
     return flags
 
 
-def decompress(group, x, flags, check_subgroup=True, out=None):
+def decompress(group, x, flags, check_subgroup=True, out=None, count_rejected=False):
     """libff's compressed points -> (points, status): x holds the X coordinates (Montgomery words, (n, 4) uint64 for "g1",
     (n, 8) for "g2"), flags one byte per point (bit 0: parity of Y / Y.c0, bit 1: is_zero).  points: (n, 12) / (n, 24)
     Jacobian with Z = one; status: PT_* per point, and every point with status >= PT_MALFORMED is (0, 1, 0).  check_subgroup
     ("g2" only): points of the twist outside G2 get PT_NOT_IN_SUBGROUP.  numpy in -> numpy out; torch CUDA tensors in -> torch
-    CUDA tensors (`out` for the points, or new), asynchronous on the library's stream, ordered after torch's current stream."""
+    CUDA tensors (`out` for the points, or new), asynchronous on the library's stream, ordered after torch's current stream.
+    count_rejected: (points, status, n_rejected) with the library's own count of the statuses >= PT_MALFORMED; the call then
+    blocks in device mode too."""
     w = _group_width(group)
     host = isinstance(x, np.ndarray)
     x, n = _point_rows(x, w // 3 * 8)
     flags = _point_flags(flags, n, host)
+    count = C.c_uint64(0)
+    pc = C.byref(count) if count_rejected else None
 
     def call(px, pf, po, ps, dev):
         if group == "g1":
-            _check(lib().lsa_g1_decompress(px, pf, n, po, ps, None, dev))
+            _check(lib().lsa_g1_decompress(px, pf, n, po, ps, pc, dev))
         else:
-            _check(lib().lsa_g2_decompress(px, pf, n, 1 if check_subgroup else 0, po, ps, None, dev))
+            _check(lib().lsa_g2_decompress(px, pf, n, 1 if check_subgroup else 0, po, ps, pc, dev))
     if host:
         if out is not None:
             raise ValueError("decompress: out is for torch CUDA tensors (numpy in gives new numpy arrays)")
         pts = np.zeros((n, w), dtype=np.uint64)
         status = np.zeros(n, dtype=np.uint8)
         call(_host_ptr(x), _host_ptr(flags), _host_ptr(pts), _host_ptr(status), 0)
-        return pts, status
+        return (pts, status, int(count.value)) if count_rejected else (pts, status)
     import torch
     if out is None:
         out = torch.empty((n, w), dtype=torch.int64, device=x.device)
@@ -550,7 +554,7 @@ def decompress(group, x, flags, check_subgroup=True, out=None):
     status = torch.empty(n, dtype=torch.uint8, device=x.device)
     _after_torch(x, flags, out)
     call(_ptr(x), _ptr(flags), _ptr(out), _ptr(status), 1)
-    return out, status
+    return (out, status, int(count.value)) if count_rejected else (out, status)
 
 
 def validate_points(group, pts, check_subgroup=True):

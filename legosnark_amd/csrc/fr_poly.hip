@@ -172,7 +172,8 @@ int lsa_fr_hadamard_quotient(const void *a, const void *b, const void *c, size_t
     rc = check_domain("fr_hadamard_quotient", big_log, small_log);
     if (rc) return rc;
     LSA_TRACE_CALL("fr_hadamard_quotient", ((size_t)1 << big_log) + (small_log >= 0 ? (size_t)1 << small_log : 0));
-    if (!a || !b || !c || !omega || !coset_g || !d123 || !h_out) { set_error("fr_hadamard_quotient: null argument"); return LSA_ERR_INVALID; }
+    // (a, b, c may be null when n == 0: an empty device tensor has no address)
+    if ((n && (!a || !b || !c)) || !omega || !coset_g || !d123 || !h_out) { set_error("fr_hadamard_quotient: null argument"); return LSA_ERR_INVALID; }
     const bool step = small_log >= 0;
     const size_t big = (size_t)1 << big_log, m = big + (step ? (size_t)1 << small_log : 0);
     if (n > m) { set_error("fr_hadamard_quotient: n = %zu values on a domain of m = %zu points", n, m); return LSA_ERR_INVALID; }

@@ -13,11 +13,13 @@ and shape, so that
 replays it.  Conditions, not measurements: a case that raises fails, none is skipped, and the number executed must be the
 number planned.  tests/test_fuzz_harness.py shows on the CPU that every kind fails when the library is one bit off.
 
-Cost: 19 kinds x 3 seeds x 50 cases = 2850 cases in 57 tests, and 3 x 190 interleaved ones (test_fuzz_parity_interleaved).
+Cost: 30 kinds x 3 seeds x 50 cases = 4500 cases in 90 tests, and 3 x 300 interleaved ones (test_fuzz_parity_interleaved).
 Oracle side alone (drawing the inputs and the oracle's answers, the library replaced by a stand-in whose own time is
 subtracted), 50 cases of the first seed on a development CPU: ORACLE_SECONDS below -- 20.4 s for the ten kinds the script
-had, 14.3 s for the nine new ones, about 35 s per seed and 105 s for the three.  Wall time of the whole module on an
-MI355X box (its CPU is the faster one): 48 s for the 60 tests, the slowest (fr_fold) 3.1 s, so no kind had to be made
+had, 14.3 s for the nine that came with the resident handles, 10.0 s for the eleven of the later provers and of key loading
+(the slowest of those, scalar_mul_batch_g2, 3.5 s), about 45 s per seed and 135 s for the three.  Wall time of the whole
+module on an MI355X box (its CPU is the faster one): 66 s for the 93 tests; the slowest are an interleaved sequence (3.5 s
+for its 300 cases) and fr_fold (3.2 s), the slowest new kind scalar_mul_batch_g2 (2.2 s), so no kind had to be made
 smaller."""
 import pytest
 
@@ -31,8 +33,10 @@ CASES = 50
 # measured, for the record (nothing asserts them): seconds for 50 cases of SEEDS[0], oracle side only
 ORACLE_SECONDS = {"final_exp": 0.7, "eq_table": 0.6, "msm": 2.6, "batch_exp": 2.9, "scalar_mul_batch": 2.7, "pairing_terms": 0.7, "ntt": 0.4, "ntt_step": 0.7,
                   "fr_fold": 8.2, "sumcheck_round": 0.9, "resident_msm": 5.1, "segments": 2.3, "commit": 5.4, "sparse_matrix_msm": 0.1, "normalize": 0.2,
-                  "sum_async": 0.2, "fq12_product": 0.1, "pairing_precomp": 0.7, "fr_scale_upper": 0.2}
-GPU_WALL_SECONDS = 48
+                  "sum_async": 0.2, "fq12_product": 0.1, "pairing_precomp": 0.7, "fr_scale_upper": 0.2,
+                  "hadamard_quotient": 2.0, "lagrange": 1.4, "fr_matvec": 0.4, "fr_matmul": 0.2, "fr_sparse_matvec": 0.2, "qap_witness": 1.1, "decompress": 0.5,
+                  "validate_points": 0.2, "compress": 0.2, "scalar_mul_batch_g2": 3.5, "sparse_matrix_msm_g2": 0.3}
+GPU_WALL_SECONDS = 66
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -49,9 +53,10 @@ INTERLEAVED_PER_KIND = 10
 
 @pytest.mark.parametrize("seed", SEEDS)
 def test_fuzz_parity_interleaved(lsa, seed):
-    """All kinds in one shuffled sequence (190 cases per seed): a call that is only wrong after some OTHER entry point ran --
+    """All kinds in one shuffled sequence (300 cases per seed): a call that is only wrong after some OTHER entry point ran --
     as the witness recursion's unzeroed last entry was, found by the script's interleaved loop and by no run of one kind
-    after the other."""
+    after the other.  Here the quotient and the witness map meet fr_ntt / fr_ntt_step on ntt.hip's shared table caches and
+    change the domain under the step domain's table of 1 / Z, and every file's grow-only staging moves between calls."""
     plan = fz.interleaved_plan(seed, INTERLEAVED_PER_KIND)
     executed, failed = 0, []
     for kind, case_seed in plan:

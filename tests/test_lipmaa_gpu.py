@@ -243,6 +243,25 @@ def test_quotient_of_shorter_vectors(lsa, key):
         assert np.array_equal(quotient(lsa, key, a, b, c, d, device=True), want), n
 
 
+@pytest.mark.parametrize("key", [(3, None), (12, None), (7, 0)], ids=str)
+def test_quotient_of_no_values_takes_empty_device_tensors(lsa, key):
+    """n = 0 in device mode: an empty tensor's address is null, and null a, b, c were refused whatever n was (found by the
+    randomised parity run: hadamard_quotient, case seed 333683051795).  All three vectors count as zero: H = d1 d2 Z - d3."""
+    import torch
+    D = dom(key)
+    d = dec(rand_fr(3, 4040 + D.m))
+    H = [0] * (D.m + 1)
+    H[0] = -d[2] % R
+    D.add_poly_Z(d[0] * d[1] % R, H)
+    none = np.zeros((0, 4), dtype=np.uint64)
+    assert np.array_equal(quotient(lsa, key, none, none, none, d), enc(H))
+    t = [torch.zeros((0, 4), dtype=torch.int64, device="cuda:0") for _ in range(3)]
+    assert all(x.data_ptr() == 0 for x in t)
+    h = lsa.fr_hadamard_quotient(t[0], t[1], t[2], enc(d), D.big_log, D.small_log, omega=D.w, coset=o.fr_mont(G))
+    lsa.synchronize()
+    assert np.array_equal(h.cpu().numpy().view(np.uint64), enc(H))
+
+
 @pytest.mark.parametrize("key", [k for k in DOMAINS if dom(k).m <= 96], ids=str)
 def test_quotient_identity_at_a_random_point(lsa, key):
     """Independent of the oracle's transforms, for c = a o b: H(x) Z(x) = (A(x) + d1 Z(x))(B(x) + d2 Z(x)) - (C(x) + d3 Z(x)) at a random x,
