@@ -1,4 +1,6 @@
-// legosnark_amd/csrc/capi.hip -- implementation of the C-ABI in include/legosnark_amd.h.
+// legosnark_amd/csrc/capi.hip -- implementation of the C-ABI in include/legosnark_amd.h: library state, bases, the CRS
+// cache and the MSM, normalise / batch_exp / sum and scalar-multiplication entry points (Fr vectors: capi_fr.hip;
+// pairings: capi_pairing.hip; host <-> device copies: host_copy.hip).
 // No CPU fallback: every compute entry point requires lsa_init() to have found a gfx950
 // device and fails with LSA_ERR_NO_DEVICE otherwise.
 #include <hip/hip_runtime.h>
@@ -20,7 +22,6 @@
 
 #include "capi_internal.h"
 #include "tower.h"
-#include "ntt_core.h"
 
 namespace lsa {
 
@@ -106,7 +107,6 @@ int require_ready() {
 
 using namespace lsa;
 
-static void release_stage_buffers();
 static void warm_stage_buffers();
 static void crs_cache_clear();
 
@@ -167,7 +167,10 @@ void lsa_shutdown(void) {
     crs_cache_clear();
     msm_release_workspace();
     batch_exp_release();
-    release_stage_buffers();
+    stage_release_all();                             // every StageBuf of every translation unit (staging.h)
+    ntt_release();                                   // the per-domain twiddle tables (ntt.hip)
+    fr_vec_release();                                // the cached hipGraphs of the Fr recursions (fr_vec.hip)
+    pairing_release();
     upload_release();
     (void)hipFree(g.d_result);
     (void)hipHostFree(g.h_result);
@@ -199,326 +202,13 @@ int lsa_profile_last_msm(float ms[LSA_MSM_STAGES]) { return msm_profile_last(ms)
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- staged host <-> device copies (capi_internal.h)
-namespace lsa {
+// grow-only device staging buffers of the host-buffer entry points (StageBuf, staging.h: lsa_shutdown frees every one)
 namespace {
-class HostCopier {
-    size_t SLOT = (size_t)2 << 20;                    // LSA_H2D_SLOT_KB (experiments)
-    static constexpr unsigned MAX_WORKERS = 12, SLOTS_PER_WORKER = 2;
-    struct Slot { void *p = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
-    struct Worker { Slot slot[SLOTS_PER_WORKER]; unsigned turn = 0; };
-    Worker w_[MAX_WORKERS];
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, cv_done_;
-    uint64_t gen_ = 0;
-    unsigned active_ = 0;
-    bool stop_ = false, broken_ = false;
-    // the job
-    char *dev_ = nullptr, *host_ = nullptr;
-    bool down_ = false;
-    size_t bytes_ = 0, nchunks_ = 0, chunk_ = 0;
-    std::atomic<size_t> next_{0};
-    std::atomic<int> err_{0};
-
-    void *arena_ = nullptr;                           // every slot, one pinned allocation
-    unsigned nworkers_ = 0;
-    // Uploads of two slots and more leave lsa_stream(): worker i issues its copies on copy stream i % ncs_, so that
-    // several copy engines run at once (one stream = one engine at a time: 23 GB/s measured, against 40-50 for the
-    // runtime's own large copy) and a kernel the caller queues on lsa_stream() between two uploads (the normalisation
-    // of the previous wave of a CRS vector) does not hold the next copies back.  run() orders the streams: they wait
-    // for what lsa_stream() holds at the start (`order_after`), lsa_stream() waits for them at the end.
-    static constexpr unsigned MAX_STREAMS = 4;
-    hipStream_t cs_[MAX_STREAMS] = {};
-    hipEvent_t ev_begin_ = nullptr, ev_done_[MAX_STREAMS] = {};
-    unsigned ncs_ = 0;
-    bool on_cs_ = false;
-    bool slot_ready(Slot &s) {
-        if (!s.p || !s.ev) return false;
-        if (s.pending) { if (hipEventSynchronize(s.ev) != hipSuccess) return false; s.pending = false; }
-        return true;
-    }
-    // threads, the pinned slots and their events, all at once (lsa_init: not inside somebody's first timed call --
-    // sixteen separate pinned allocations took 8 ms of the unchanged hadamard's Lipmaa prover)
-    bool prepare_locked() {
-        if (arena_) return true;
-        const unsigned hw = std::thread::hardware_concurrency();
-        const char *e = getenv("LSA_H2D_THREADS");
-        // one thread moves ~10 GB/s through a pinned slot; the link takes ~55: ten on a host with cores to spare
-        unsigned want = e ? (unsigned)atoi(e) : (hw >= 32 ? 10 : (hw > 8 ? 6 : (hw > 2 ? hw / 2 : 1)));
-        if (want < 1) want = 1;
-        if (want > MAX_WORKERS) want = MAX_WORKERS;
-        if (const char *sk = getenv("LSA_H2D_SLOT_KB")) { const size_t kb = (size_t)atol(sk); if (kb >= 64 && kb <= 16384) SLOT = kb << 10; }
-        if (hipHostMalloc(&arena_, (size_t)want * SLOTS_PER_WORKER * SLOT, hipHostMallocDefault) != hipSuccess) { arena_ = nullptr; return false; }
-        for (unsigned i = 0; i < want; i++)
-            for (unsigned k = 0; k < SLOTS_PER_WORKER; k++) {
-                Slot &s = w_[i].slot[k];
-                s.p = (char *)arena_ + ((size_t)i * SLOTS_PER_WORKER + k) * SLOT;
-                s.pending = false;
-                if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) { s.ev = nullptr; return false; }
-            }
-        nworkers_ = want;
-        const char *se = getenv("LSA_H2D_STREAMS");
-        // ONE copy stream by default: enough to run the copies beside the kernels of lsa_stream() (96 MiB of first-sight
-        // bases: 3.3 ms, 4.3 on lsa_stream() itself); with two to four, 40 % of the first calls of fresh processes took
-        // another 7 ms (more copy engines and queues brought up lazily, in whichever call first overlaps enough copies)
-        unsigned ns = se ? (unsigned)atoi(se) : 1u;
-        if (ns > MAX_STREAMS) ns = MAX_STREAMS;
-        if (ns > want) ns = want;
-        ncs_ = 0;
-        if (ns && hipEventCreateWithFlags(&ev_begin_, hipEventDisableTiming) == hipSuccess) {
-            for (unsigned k = 0; k < ns; k++) {
-                if (hipStreamCreateWithFlags(&cs_[k], hipStreamNonBlocking) != hipSuccess) { cs_[k] = nullptr; break; }
-                if (hipEventCreateWithFlags(&ev_done_[k], hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(cs_[k]); cs_[k] = nullptr; ev_done_[k] = nullptr; break; }
-                ncs_ = k + 1;
-            }
-        }
-        (void)hipGetLastError();
-        for (unsigned i = 1; i < want; i++) th_.emplace_back([this, i] { loop(i); });
-        return true;
-    }
-    void work(unsigned id) {
-        if (id) (void)hipSetDevice(g.device);
-        Worker &w = w_[id];
-        for (;;) {
-            const size_t c = next_.fetch_add(1);
-            if (c >= nchunks_) break;
-            const size_t lo = c * chunk_, len = bytes_ - lo < chunk_ ? bytes_ - lo : chunk_;
-            Slot &s = w.slot[w.turn++ % SLOTS_PER_WORKER];
-            if (!slot_ready(s)) { err_ = 1; continue; }
-            if (down_) {
-                if (hipMemcpyAsync(s.p, dev_ + lo, len, hipMemcpyDeviceToHost, g.stream) != hipSuccess || hipEventRecord(s.ev, g.stream) != hipSuccess ||
-                    hipEventSynchronize(s.ev) != hipSuccess) { err_ = 1; continue; }
-                memcpy(host_ + lo, s.p, len);
-            } else {
-                hipStream_t st = on_cs_ ? cs_[id % ncs_] : g.stream;
-                memcpy(s.p, host_ + lo, len);
-                if (hipMemcpyAsync(dev_ + lo, s.p, len, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(s.ev, st) != hipSuccess) { err_ = 1; continue; }
-                s.pending = true;
-            }
-        }
-    }
-    void loop(unsigned id) {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-            }
-            work(id);
-            {
-                std::lock_guard<std::mutex> lk(m_);
-                if (--active_ == 0) cv_done_.notify_all();
-            }
-        }
-    }
-
-  public:
-    ~HostCopier() { stop_threads(); }
-    // 0: done (up: every copy is on the stream; down: the bytes are in host memory), 1: not taken, < 0: LSA error
-    int run(void *dev, void *host, size_t bytes, bool down, bool order_after = true) {
-        if (broken_) return 1;
-        dev_ = (char *)dev; host_ = (char *)host; bytes_ = bytes; down_ = down;
-        // whole slots for large copies; a copy of 0.5 .. 4 MiB (the points of a 2^12-pair product: 0.4 + 0.8 MiB) is cut into
-        // up to four pieces of >= 256 KiB so that its memcpy is shared too (one thread moves ~10 GB/s: 80 us per 0.8 MiB)
-        chunk_ = SLOT;
-        if (bytes >= ((size_t)512 << 10) && bytes < 2 * SLOT) {
-            const size_t pieces = bytes / ((size_t)256 << 10) < 4 ? bytes / ((size_t)256 << 10) : 4;
-            chunk_ = ((bytes + pieces - 1) / pieces + 4095) & ~(size_t)4095;
-            if (chunk_ > SLOT) chunk_ = SLOT;
-        }
-        nchunks_ = (bytes + chunk_ - 1) / chunk_;
-        next_.store(0);
-        err_.store(0);
-        bool alone = nchunks_ < 2;                        // one piece: not worth waking anybody
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            if (!prepare_locked()) { broken_ = true; return 1; }
-            if (th_.empty()) alone = true;
-            on_cs_ = !down && !alone && ncs_ > 0;
-            if (on_cs_ && order_after) {
-                bool ok = hipEventRecord(ev_begin_, g.stream) == hipSuccess;
-                for (unsigned k = 0; k < ncs_ && ok; k++) ok = hipStreamWaitEvent(cs_[k], ev_begin_, 0) == hipSuccess;
-                if (!ok) { (void)hipGetLastError(); on_cs_ = false; }
-            }
-            if (!alone) {
-                active_ = (unsigned)th_.size();
-                gen_++;
-            }
-        }
-        if (!alone) cv_.notify_all();
-        work(0);
-        if (!alone) {
-            std::unique_lock<std::mutex> lk(m_);
-            cv_done_.wait(lk, [&] { return active_ == 0; });
-        }
-        if (on_cs_) {
-            for (unsigned k = 0; k < ncs_; k++)
-                if (hipEventRecord(ev_done_[k], cs_[k]) != hipSuccess || hipStreamWaitEvent(g.stream, ev_done_[k], 0) != hipSuccess) err_ = 1;
-            on_cs_ = false;
-        }
-        if (err_.load()) {
-            broken_ = true;
-            set_error("a staged host <-> device copy failed (%s)", hipGetErrorString(hipGetLastError()));
-            return LSA_ERR_HIP;
-        }
-        return 0;
-    }
-    void stop_threads() {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) if (t.joinable()) t.join();
-        th_.clear();
-        std::lock_guard<std::mutex> lk(m_);
-        stop_ = false;
-        gen_ = 0;
-        active_ = 0;
-    }
-    void prepare() {
-        std::lock_guard<std::mutex> lk(m_);
-        if (!prepare_locked()) broken_ = true;
-    }
-    // the first pinned transfer on a stream sets up that stream's copy-engine queue (~7 ms each, measured inside the
-    // first CRS upload of a process): paid in lsa_init, per copy stream and per size class a slot can carry
-    // (the runtime adds copy engines when copies overlap, and each new engine is another such set-up: the warm-up keeps
-    // every copy stream busy at the same time, ordered against lsa_stream() exactly as run() orders them)
-    void warm_streams() {
-        std::lock_guard<std::mutex> lk(m_);
-        if (!arena_ || !ncs_) return;
-        void *d = nullptr;
-        if (hipMalloc(&d, (size_t)ncs_ * SLOT) != hipSuccess) { (void)hipGetLastError(); return; }
-        (void)hipEventRecord(ev_begin_, g.stream);
-        for (unsigned k = 0; k < ncs_; k++) (void)hipStreamWaitEvent(cs_[k], ev_begin_, 0);
-        for (int rep = 0; rep < 12; rep++)
-            for (unsigned k = 0; k < ncs_; k++)
-                (void)hipMemcpyAsync((char *)d + (size_t)k * SLOT, (char *)arena_ + (size_t)k * SLOT, rep & 1 ? SLOT / 4 : SLOT, hipMemcpyHostToDevice, cs_[k]);
-        for (unsigned k = 0; k < ncs_; k++) { (void)hipEventRecord(ev_done_[k], cs_[k]); (void)hipStreamWaitEvent(g.stream, ev_done_[k], 0); }
-        (void)hipStreamSynchronize(g.stream);
-        for (unsigned k = 0; k < ncs_; k++) (void)hipStreamSynchronize(cs_[k]);
-        (void)hipFree(d);
-        (void)hipGetLastError();
-    }
-    void release() {
-        stop_threads();
-        for (auto &w : w_)
-            for (auto &s : w.slot) {
-                if (s.ev) { if (s.pending) (void)hipEventSynchronize(s.ev); (void)hipEventDestroy(s.ev); }
-                s = Slot();
-            }
-        for (unsigned k = 0; k < MAX_STREAMS; k++) {
-            if (cs_[k]) { (void)hipStreamSynchronize(cs_[k]); (void)hipStreamDestroy(cs_[k]); }
-            if (ev_done_[k]) (void)hipEventDestroy(ev_done_[k]);
-            cs_[k] = nullptr; ev_done_[k] = nullptr;
-        }
-        if (ev_begin_) (void)hipEventDestroy(ev_begin_);
-        ev_begin_ = nullptr;
-        ncs_ = 0;
-        if (arena_) (void)hipHostFree(arena_);
-        arena_ = nullptr;
-        nworkers_ = 0;
-        broken_ = false;
-    }
-};
-HostCopier g_copier;
-// 0 auto, 1 direct, 2 staged at every size
-int copy_mode() {
-    static const int mode = [] {
-        const char *e = getenv("LSA_H2D");
-        return !e ? 0 : (strcmp(e, "direct") == 0 ? 1 : (strcmp(e, "staged") == 0 ? 2 : 0));
-    }();
-    return mode;
-}
-constexpr size_t STAGE_FROM = (size_t)32 << 10;       // below: the runtime copies through its own staging buffer
-// from here on the runtime's own path (pin the caller's pages, one DMA) wins: a staged copy is sixteen and more
-// commands and six threads of memcpy -- 32 MiB: 0.3-0.4 ms later on the device than the direct copy, and the
-// fingerprint threads get less of the host.  (Buffers this large are the ones whose release stalls the GPU when the
-// runtime has pinned them: see capi_internal.h; the shim keeps them on the heap, other callers keep them alive.)
-constexpr size_t STAGE_BELOW = (size_t)16 << 20;
-static bool staged(size_t bytes) { return copy_mode() != 1 && ((bytes >= STAGE_FROM && bytes < STAGE_BELOW) || copy_mode() == 2); }
-// A host range the library has NOT been handed before (the reference's provers: one multiExpMA per key vector and
-// process, src/gadgets/subspace.cc:78-85; fresh std::vectors of scalars per call) is the other case: the runtime's direct
-// path first has to pin its pages, 4 KiB at a time unless the kernel backs the range with huge pages -- 5-20 ms per
-// 96 MiB depending on the box, where the slots move it at the link rate whatever the pages are.  The last few large
-// ranges are remembered; a range goes through the slots until it has been seen LSA_H2D_DIRECT_AFTER (default 2) times,
-// from then on the runtime's registration is worth its price (bench loops, provers that keep their vectors).
-struct SeenRange { const void *p = nullptr; size_t bytes = 0; unsigned count = 0; uint64_t tick = 0; };
-static SeenRange g_seen[16];
-static uint64_t g_seen_tick = 0;
-static unsigned direct_after() {
-    static const unsigned v = [] { const char *e = getenv("LSA_H2D_DIRECT_AFTER"); return e ? (unsigned)atoi(e) : 2u; }();
-    return v;
-}
-static bool large_copy_staged(const void *h, size_t bytes) {
-    if (copy_mode() == 1) return false;
-    if (copy_mode() == 2) return true;
-    SeenRange *slot = &g_seen[0];
-    for (auto &r : g_seen) {
-        if (r.p == h && r.bytes == bytes) { r.tick = ++g_seen_tick; return r.count++ < direct_after(); }
-        if (r.tick < slot->tick) slot = &r;
-    }
-    *slot = SeenRange{h, bytes, 1, ++g_seen_tick};
-    return direct_after() > 0;
-}
+StageBuf g_stage_jac, g_stage_bases, g_stage_scalars, g_stage_prefix_scratch;
 }  // namespace
+namespace lsa { StageBuf g_stage_gather; }
 
-bool upload_takes_slots(const void *h_src, size_t bytes) {
-    return staged(bytes) || (bytes >= STAGE_BELOW && large_copy_staged(h_src, bytes));
-}
-int upload_host_as(void *d_dst, const void *h_src, size_t bytes, bool slots, bool order_after) {
-    if (bytes == 0) return LSA_OK;
-    if (slots) {
-        const int rc = g_copier.run(d_dst, const_cast<void *>(h_src), bytes, false, order_after);
-        if (rc <= 0) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, g.stream));
-    return LSA_OK;
-}
-int upload_host(void *d_dst, const void *h_src, size_t bytes) {
-    return upload_host_as(d_dst, h_src, bytes, bytes != 0 && upload_takes_slots(h_src, bytes), true);
-}
-int download_host(void *h_dst, const void *d_src, size_t bytes) {
-    if (bytes == 0) return LSA_OK;
-    // (large destinations the library has not seen before go through the slots as well: the runtime would pin the caller's
-    // pages and keep them registered, and a caller that frees such a buffer afterwards -- a Python array, a temporary
-    // std::vector outside the shim's allocator settings -- stalls its next GPU submission by 12-25 ms when the pages are
-    // unmapped: measured as a 15.5 ms bubble in front of the first MSM after a 96-MiB download, 26 ms after 192 MiB)
-    if (staged(bytes) || (bytes >= STAGE_BELOW && large_copy_staged(h_dst, bytes))) {
-        const int rc = g_copier.run(const_cast<void *>(d_src), h_dst, bytes, true);
-        if (rc <= 0) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    return LSA_OK;
-}
-void upload_release() { g_copier.release(); }
-void upload_prepare() {
-    if (copy_mode() == 1) return;
-    g_copier.prepare();
-    // the runtime sets up a copy engine's queue at the first pinned transfer of a direction and size class (measured:
-    // 8.4 ms inside the first 128-KiB download of a process that had only done larger ones; none with
-    // HSA_ENABLE_SDMA=0): pay that here for every size a slot can carry, not inside a caller's first NTT
-    void *d = nullptr;
-    if (hipMalloc(&d, (size_t)4 << 20) != hipSuccess) { (void)hipGetLastError(); return; }
-    g_copier.warm_streams();
-    std::vector<char> h((size_t)4 << 20, 0);
-    for (size_t bytes = STAGE_FROM; bytes <= ((size_t)4 << 20); bytes <<= 1) {
-        if (upload_host(d, h.data(), bytes) != LSA_OK) break;
-        (void)hipStreamSynchronize(g.stream);                       // (a download on an idle stream takes another path)
-        if (download_host(h.data(), d, bytes) != LSA_OK) break;
-    }
-    (void)hipStreamSynchronize(g.stream);
-    (void)hipFree(d);
-}
-}  // namespace lsa
-extern "C" {
 // ---------------------------------------------------------------- bases
-}  // extern "C"
-static int stage_jac_ensure(size_t bytes, void **p);      // g_stage_jac (below)
 template <class F>
 static int bases_create(const void *bases_jac, size_t n, int src_on_device, int group, lsa_bases **out, bool allow_table = true) {
     int rc = require_ready();
@@ -559,7 +249,7 @@ static int bases_create(const void *bases_jac, size_t n, int src_on_device, int 
             const size_t jbytes = n * sizeof(Jac<F>);
             void *d_stage = nullptr;
             if (jbytes <= ((size_t)512 << 20)) {
-                if (stage_jac_ensure(jbytes, &d_stage)) d_stage = nullptr;
+                if (!g_stage_jac.ensure(jbytes)) d_stage = g_stage_jac.p;
             }
             if (!d_stage) {
                 if (hipMalloc(&tmp, jbytes) != hipSuccess) {
@@ -692,22 +382,6 @@ int lsa_msm_run(const lsa_bases *bases, size_t first, const void *d_scalars, siz
 }
 
 }  // extern "C"
-// grow-only device staging buffers of the host-buffer entry points (StageBuf, capi_internal.h)
-namespace {
-StageBuf g_stage_jac, g_stage_bases, g_stage_scalars, g_stage_prefix_scratch;
-StageBuf g_stage_ntt_a, g_stage_ntt_tmp;         // lsa_fr_ntt: the data of host callers, the second buffer of the passes
-// the Fr recursions (lsa_fr_cppoly_witness, lsa_fr_eval_mle): scratch, and for host callers v / r / w -- grow-only like the
-// others (round 5; before, every call paid a hipMalloc + hipFree pair per buffer, and the recursions' cached hipGraphs
-// (fr_vec.hip) are keyed by these pointers)
-StageBuf g_stage_fr_tmp, g_stage_fr_v, g_stage_fr_r, g_stage_fr_w;
-StageBuf g_stage_sc_partial, g_stage_sc_out;     // lsa_fr_sumcheck_round: block partials and the coefficients (one call per round of a prover)
-}  // namespace
-namespace lsa { StageBuf g_stage_gather; }
-static int stage_jac_ensure(size_t bytes, void **p) {
-    if (g_stage_jac.ensure(bytes)) return -1;
-    *p = g_stage_jac.p;
-    return 0;
-}
 // lsa_init: the staging buffers of the host-vector entry points at the BASELINE scale (2^20 scalars, 2^20 G2 points in
 // Jacobian form), beside msm_warmup's workspaces: no allocation inside a prover's first multiExpMA (LSA_WARM=0: lazy)
 static void warm_stage_buffers() {
@@ -720,19 +394,6 @@ static void warm_stage_buffers() {
     const int e1 = g_stage_scalars.ensure(((size_t)34 << 20) * scale / 400), e2 = g_stage_jac.ensure(((size_t)202 << 20) * scale / 400);
     if ((e1 || e2) && trace_on()) fprintf(stderr, "[lsa]   warm-up: staging buffers not allocated\n");
     (void)hipGetLastError();
-}
-static void release_stage_buffers() {
-    g_stage_jac.release(); g_stage_bases.release(); g_stage_scalars.release(); g_stage_gather.release(); g_stage_prefix_scratch.release();
-    g_stage_ntt_a.release(); g_stage_ntt_tmp.release();
-    g_stage_fr_tmp.release(); g_stage_fr_v.release(); g_stage_fr_r.release(); g_stage_fr_w.release();
-    g_stage_sc_partial.release(); g_stage_sc_out.release();
-    ntt_release();                                   // the per-domain twiddle tables (ntt.hip)
-    fr_vec_release();                                // the cached hipGraphs of the Fr recursions (fr_vec.hip)
-    pairing_release();
-    fr_poly_release();
-    fr_matrix_release();
-    fr_sparse_release();
-    point_load_release();
 }
 
 // ---------------------------------------------------------------- CRS cache behind lsa_g1_msm / lsa_g2_msm
@@ -1589,14 +1250,6 @@ int lsa_g2_sum_async(const void *d_pts, size_t n, void *d_out) {
 }
 }  // extern "C"
 
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? 0 : -1; }
-};
-}  // namespace
-
 // ---------------------------------------------------------------- variable-base scalar mul / sparse matrix
 namespace {
 inline int smul_device(const Jac<Fq> *p, const Fr *s, const uint32_t *idx, size_t n, Jac<Fq> *o, hipStream_t st) { return g1_scalar_mul_device(p, s, idx, n, o, st); }
@@ -1613,18 +1266,15 @@ int scalar_mul_batch(const void *pts_jac, const void *scalars, size_t n, void *o
     if (!pts_jac || !scalars || !out_jac) { set_error("scalar_mul_batch: null argument"); return LSA_ERR_INVALID; }
     rc = msm_join(g.stream);
     if (rc) return rc;
-    if (on_device) return smul_device((const Jac<F> *)pts_jac, (const Fr *)scalars, nullptr, n, (Jac<F> *)out_jac, g.stream);
     DevBuf d_p, d_s, d_o;
-    if (d_p.alloc(n * sizeof(Jac<F>)) || d_s.alloc(n * sizeof(Fr)) || d_o.alloc(n * sizeof(Jac<F>))) {
-        set_error("scalar_mul_batch: hipMalloc failed");
-        return LSA_ERR_NOMEM;
-    }
-    LSA_UPLOAD(d_p.p, pts_jac, n * sizeof(Jac<F>));
-    LSA_UPLOAD(d_s.p, scalars, n * sizeof(Fr));
-    rc = smul_device((const Jac<F> *)d_p.p, (const Fr *)d_s.p, nullptr, n, (Jac<F> *)d_o.p, g.stream);
+    OperandFrame f("scalar_mul_batch", on_device);
+    const Jac<F> *p = f.in<Jac<F>>(d_p, pts_jac, n * sizeof(Jac<F>));
+    const Fr *s = f.in<Fr>(d_s, scalars, n * sizeof(Fr));
+    Jac<F> *o = f.out<Jac<F>>(d_o, out_jac, n * sizeof(Jac<F>));
+    if (f.rc()) return f.rc();
+    rc = smul_device(p, s, nullptr, n, o, g.stream);
     if (rc) return rc;
-    LSA_DOWNLOAD(out_jac, d_o.p, n * sizeof(Jac<F>));
-    return LSA_OK;
+    return f.download();
 }
 
 // the body of lsa_g1_sparse_matrix_msm / lsa_g2_sparse_matrix_msm
@@ -1645,24 +1295,20 @@ int sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const uint64_t
     rc = msm_join(g.stream);
     if (rc) return rc;
     DevBuf d_v, d_r, d_c, d_e, d_items, d_o;
-    if (d_v.alloc(nnz * sizeof(Jac<F>)) || d_r.alloc(nnz * sizeof(uint32_t)) || d_c.alloc((ncols + 1) * sizeof(uint64_t)) ||
-        d_e.alloc(nrows * sizeof(Fr)) || d_items.alloc(nnz * sizeof(Jac<F>)) || d_o.alloc(ncols * sizeof(Jac<F>))) {
-        set_error("sparse_matrix_msm: hipMalloc failed");
-        return LSA_ERR_NOMEM;
-    }
-    if (nnz) {
-        LSA_UPLOAD(d_v.p, vals_jac, nnz * sizeof(Jac<F>));
-        LSA_UPLOAD(d_r.p, rows, nnz * sizeof(uint32_t));
-        LSA_UPLOAD(d_e.p, exps, nrows * sizeof(Fr));
-    }
-    LSA_UPLOAD(d_c.p, col_ptr, (ncols + 1) * sizeof(uint64_t));
-    rc = smul_device((const Jac<F> *)d_v.p, (const Fr *)d_e.p, (const uint32_t *)d_r.p, nnz, (Jac<F> *)d_items.p, g.stream);
+    OperandFrame f("sparse_matrix_msm", /*on_device=*/0);            // (host buffers only; the exponents go up only with entries to use them)
+    const Jac<F> *v = f.in<Jac<F>>(d_v, vals_jac, nnz * sizeof(Jac<F>));
+    const uint32_t *r = f.in<uint32_t>(d_r, rows, nnz * sizeof(uint32_t));
+    const Fr *e = f.in<Fr>(d_e, exps, nnz ? nrows * sizeof(Fr) : 0, nrows * sizeof(Fr));
+    const uint64_t *c = f.in<uint64_t>(d_c, col_ptr, (ncols + 1) * sizeof(uint64_t));
+    Jac<F> *items = f.scratch<Jac<F>>(d_items, nnz * sizeof(Jac<F>));
+    Jac<F> *o = f.out<Jac<F>>(d_o, out_jac, ncols * sizeof(Jac<F>));
+    if (f.rc()) return f.rc();
+    rc = smul_device(v, e, r, nnz, items, g.stream);
     if (rc) return rc;
-    rc = colsum_device((const Jac<F> *)d_items.p, (const uint64_t *)d_c.p, ncols, (Jac<F> *)d_o.p, g.stream);
+    rc = colsum_device(items, c, ncols, o, g.stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(out_jac, d_o.p, ncols * sizeof(Jac<F>));
-    return LSA_OK;
+    return f.download();
 }
 }  // namespace
 
@@ -1692,208 +1338,5 @@ size_t lsa_smul_param(int which) {
     case LSA_SMUL_PARAM_G2_LANES_PER_ITEM: return g2_smul_param(2);
     }
     return 0;
-}
-}  // extern "C"
-
-// ---------------------------------------------------------------- Fr vectors
-extern "C" {
-int lsa_fr_cppoly_witness(const void *v, size_t d, const void *r, void *w, int on_device) {
-    LSA_TRACE_CALL("fr_cppoly_witness", (size_t)1 << d);
-    int rc = require_ready();
-    if (rc) return rc;
-    if (d > 40) { set_error("cppoly_witness: d = %zu too large", d); return LSA_ERR_INVALID; }
-    if (!v || !w || (d && !r)) { set_error("cppoly_witness: null argument"); return LSA_ERR_INVALID; }
-    const size_t N = (size_t)1 << d;
-    StageBuf &d_tmp = g_stage_fr_tmp, &d_v = g_stage_fr_v, &d_r = g_stage_fr_r, &d_w = g_stage_fr_w;
-    if (d_tmp.ensure((N / 2 + N / 4 + 1) * sizeof(Fr))) { set_error("cppoly_witness: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (on_device) {
-        rc = fr_cppoly_fold_device((const Fr *)v, d, (const Fr *)r, (Fr *)w, (Fr *)d_tmp.p, g.stream);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(g.stream));   // (callers read w from their own streams)
-        return LSA_OK;
-    }
-    if (d_v.ensure(N * sizeof(Fr)) || d_r.ensure((d + 1) * sizeof(Fr)) || d_w.ensure(N * sizeof(Fr))) { set_error("cppoly_witness: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    LSA_UPLOAD(d_v.p, v, N * sizeof(Fr));
-    if (d) LSA_UPLOAD(d_r.p, r, d * sizeof(Fr));
-    rc = fr_cppoly_fold_device((const Fr *)d_v.p, d, (const Fr *)d_r.p, (Fr *)d_w.p, (Fr *)d_tmp.p, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(w, d_w.p, N * sizeof(Fr));
-    return LSA_OK;
-}
-
-int lsa_fr_eval_mle(const void *v, size_t d, const void *r, void *out, int on_device) {
-    LSA_TRACE_CALL("fr_eval_mle", (size_t)1 << d);
-    int rc = require_ready();
-    if (rc) return rc;
-    if (d > 40) { set_error("eval_mle: d = %zu too large", d); return LSA_ERR_INVALID; }
-    if (!v || !out || (d && !r)) { set_error("eval_mle: null argument"); return LSA_ERR_INVALID; }
-    const size_t N = (size_t)1 << d;
-    StageBuf &d_tmp = g_stage_fr_tmp, &d_v = g_stage_fr_v, &d_r = g_stage_fr_r, &d_o = g_stage_fr_w;
-    if (d_tmp.ensure((N / 2 + N / 4 + 1) * sizeof(Fr))) { set_error("eval_mle: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (on_device) {
-        rc = fr_eval_mle_device((const Fr *)v, d, (const Fr *)r, (Fr *)d_tmp.p, (Fr *)out, g.stream);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(g.stream));
-        return LSA_OK;
-    }
-    if (d_v.ensure(N * sizeof(Fr)) || d_r.ensure((d + 1) * sizeof(Fr)) || d_o.ensure(sizeof(Fr))) { set_error("eval_mle: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    LSA_UPLOAD(d_v.p, v, N * sizeof(Fr));
-    if (d) LSA_UPLOAD(d_r.p, r, d * sizeof(Fr));
-    rc = fr_eval_mle_device((const Fr *)d_v.p, d, (const Fr *)d_r.p, (Fr *)d_tmp.p, (Fr *)d_o.p, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(out, d_o.p, sizeof(Fr));
-    return LSA_OK;
-}
-
-int lsa_fr_sumcheck_round(const void *suff, const void *const *tables, size_t m, size_t half, const void *pre, const void *rho_j,
-                          void *out_coeffs, int on_device) {
-    int rc = require_ready();
-    if (rc) return rc;
-    if (!tables || !out_coeffs || m == 0 || m > 4 || half == 0) { set_error("sumcheck_round: invalid argument (1 <= m <= 4, half > 0)"); return LSA_ERR_INVALID; }
-    if (rho_j && !pre) { set_error("sumcheck_round: rho_j without pre"); return LSA_ERR_INVALID; }
-    for (size_t t = 0; t < m; t++) if (!tables[t]) { set_error("sumcheck_round: null table"); return LSA_ERR_INVALID; }
-    const size_t ncoef = m + (rho_j ? 2 : 1);
-    StageBuf &d_partial = g_stage_sc_partial, &d_out = g_stage_sc_out;
-    DevBuf d_suff, d_tab[4];
-    if (d_partial.ensure(fr_sumcheck_scratch_elems() * sizeof(Fr)) || d_out.ensure(8 * sizeof(Fr))) { set_error("sumcheck_round: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    const Fr *tabs[4] = {nullptr, nullptr, nullptr, nullptr};
-    const Fr *sf = (const Fr *)suff;
-    if (on_device) {
-        for (size_t t = 0; t < m; t++) tabs[t] = (const Fr *)tables[t];
-    } else {
-        for (size_t t = 0; t < m; t++) {
-            if (d_tab[t].alloc(2 * half * sizeof(Fr))) { set_error("sumcheck_round: hipMalloc failed"); return LSA_ERR_NOMEM; }
-            LSA_UPLOAD(d_tab[t].p, tables[t], 2 * half * sizeof(Fr));
-            tabs[t] = (const Fr *)d_tab[t].p;
-        }
-        if (suff) {
-            if (d_suff.alloc(half * sizeof(Fr))) { set_error("sumcheck_round: hipMalloc failed"); return LSA_ERR_NOMEM; }
-            LSA_UPLOAD(d_suff.p, suff, half * sizeof(Fr));
-            sf = (const Fr *)d_suff.p;
-        }
-    }
-    rc = fr_sumcheck_round_device(sf, tabs, m, half, (const Fr *)pre, (const Fr *)rho_j, (Fr *)d_partial.p, (Fr *)d_out.p, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(out_coeffs, d_out.p, ncoef * sizeof(Fr));
-    return LSA_OK;
-}
-
-int lsa_fr_scale_upper(const void *old, size_t half, const void *k, void *cur, int on_device) {
-    LSA_TRACE_CALL("fr_scale_upper", half);
-    int rc = require_ready();
-    if (rc) return rc;
-    if (half == 0) return LSA_OK;
-    if (!old || !cur || !k) { set_error("fr_scale_upper: null argument"); return LSA_ERR_INVALID; }
-    Fr kk;
-    memcpy(&kk, k, sizeof kk);
-    if (on_device) return fr_scale_upper_device((const Fr *)old, half, kk, (Fr *)cur, g.stream);
-    DevBuf d_v;
-    if (d_v.alloc(2 * half * sizeof(Fr))) { set_error("fr_scale_upper: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    LSA_UPLOAD(d_v.p, old, 2 * half * sizeof(Fr));
-    rc = fr_scale_upper_device((const Fr *)d_v.p, half, kk, (Fr *)d_v.p, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(cur, d_v.p, half * sizeof(Fr));
-    return LSA_OK;
-}
-
-int lsa_fr_eq_table(const void *r, size_t d, int variant, void *out, int on_device) {
-    LSA_TRACE_CALL("fr_eq_table", (size_t)1 << (d & 63));
-    int rc = require_ready();
-    if (rc) return rc;
-    if (d == 0 || d > 30) { set_error("fr_eq_table: need 1 <= d <= 30 (got %zu)", d); return LSA_ERR_INVALID; }
-    if (!out || (d && !r)) { set_error("fr_eq_table: null argument"); return LSA_ERR_INVALID; }
-    if (variant != 0 && variant != 1) { set_error("fr_eq_table: variant %d (0: the reference's loop, 1: the eq monomials)", variant); return LSA_ERR_INVALID; }
-    const size_t N = (size_t)1 << d;
-    StageBuf &d_tmp = g_stage_fr_tmp, &d_r = g_stage_fr_r, &d_o = g_stage_fr_w;
-    if (d_tmp.ensure(fr_eq_table_scratch_elems(d) * sizeof(Fr))) { set_error("fr_eq_table: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (on_device) return fr_eq_table_device((const Fr *)r, d, variant, (Fr *)d_tmp.p, (Fr *)out, g.stream);
-    if (d_r.ensure((d + 1) * sizeof(Fr)) || d_o.ensure(N * sizeof(Fr))) { set_error("fr_eq_table: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (d) LSA_UPLOAD(d_r.p, r, d * sizeof(Fr));
-    rc = fr_eq_table_device((const Fr *)d_r.p, d, variant, (Fr *)d_tmp.p, (Fr *)d_o.p, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(out, d_o.p, N * sizeof(Fr));
-    return LSA_OK;
-}
-
-int lsa_fr_ntt(void *a, size_t log_n, const void *omega, int inverse, const void *coset_g, int on_device) {
-    LSA_TRACE_CALL("fr_ntt", (size_t)1 << log_n);
-    int rc = require_ready();
-    if (rc) return rc;
-    if (log_n > 28) { set_error("fr_ntt: log_n = %zu exceeds the 2-adicity of Fr (28)", log_n); return LSA_ERR_INVALID; }
-    if (!a || !omega) { set_error("fr_ntt: null argument"); return LSA_ERR_INVALID; }
-    if (log_n == 0) return LSA_OK;
-    const size_t n = (size_t)1 << log_n;
-    Fr w, gco;
-    memcpy(&w, omega, sizeof w);
-    if (coset_g) memcpy(&gco, coset_g, sizeof gco);
-    // grow-only staging (released by lsa_shutdown, like every other staging buffer) for the second buffer of the passes
-    // and, for host callers, the data: two hipMalloc / hipFree pairs per call cost a 2^20-point transform of an unchanged
-    // prover more than its kernels (the shim's evaluation_domain calls this 7 times per Lipmaa proof).  The twiddle
-    // tables are cached per domain inside ntt.hip.
-    StageBuf &s_a = g_stage_ntt_a;
-    if (log_n > NTT_TILE_LOG && g_stage_ntt_tmp.ensure(n * sizeof(Fr))) { set_error("fr_ntt: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    Fr *da = (Fr *)a;
-    if (!on_device) {
-        if (s_a.ensure(n * sizeof(Fr))) { set_error("fr_ntt: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        LSA_UPLOAD(s_a.p, a, n * sizeof(Fr));
-        da = (Fr *)s_a.p;
-    }
-    rc = fr_ntt_device(da, (unsigned)log_n, w, inverse != 0, coset_g ? &gco : nullptr, (Fr *)g_stage_ntt_tmp.p, g.stream);
-    if (rc) return rc;
-    // (The download is enqueued BEHIND the kernels, not after a wait for them: the first device -> host copy a process
-    // issues on an idle stream costs it 8 ms of copy-engine set-up on this stack.)
-    if (!on_device) LSA_DOWNLOAD(a, s_a.p, n * sizeof(Fr));
-    else HIPCHK(hipStreamSynchronize(g.stream));
-    return LSA_OK;
-}
-
-int lsa_fr_ntt_step(void *a, size_t big_log, size_t small_log, const void *omega, int inverse, const void *coset_g, int on_device) {
-    LSA_TRACE_CALL("fr_ntt_step", ((size_t)1 << (big_log & 31)) + ((size_t)1 << (small_log & 31)));
-    int rc = require_ready();
-    if (rc) return rc;
-    if (big_log > 27 || small_log >= big_log) {
-        set_error("fr_ntt_step: need small_log < big_log <= 27 (got %zu, %zu): omega is a 2^(big_log + 1)-th root of unity of a field of 2-adicity 28", small_log, big_log);
-        return LSA_ERR_INVALID;
-    }
-    if (!a || !omega) { set_error("fr_ntt_step: null argument"); return LSA_ERR_INVALID; }
-    const size_t big = (size_t)1 << big_log, m = big + ((size_t)1 << small_log);
-    Fr w, gco;
-    memcpy(&w, omega, sizeof w);
-    if (coset_g) memcpy(&gco, coset_g, sizeof gco);
-    if (g_stage_ntt_tmp.ensure(big * sizeof(Fr))) { set_error("fr_ntt_step: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    Fr *da = (Fr *)a;
-    if (!on_device) {
-        if (g_stage_ntt_a.ensure(m * sizeof(Fr))) { set_error("fr_ntt_step: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        LSA_UPLOAD(g_stage_ntt_a.p, a, m * sizeof(Fr));
-        da = (Fr *)g_stage_ntt_a.p;
-    }
-    rc = fr_ntt_step_device(da, (unsigned)big_log, (unsigned)small_log, w, inverse != 0, coset_g ? &gco : nullptr, (Fr *)g_stage_ntt_tmp.p, g.stream);
-    if (rc) return rc;
-    if (!on_device) LSA_DOWNLOAD(a, g_stage_ntt_a.p, m * sizeof(Fr));
-    else HIPCHK(hipStreamSynchronize(g.stream));
-    return LSA_OK;
-}
-
-int lsa_fr_fold(const void *old, size_t half, const void *r, void *cur, int on_device) {
-    LSA_TRACE_CALL("fr_fold", half);
-    int rc = require_ready();
-    if (rc) return rc;
-    if (half == 0) return LSA_OK;
-    if (!old || !cur || !r) { set_error("fr_fold: null argument"); return LSA_ERR_INVALID; }
-    if (on_device) return fr_fold_halves_device((const Fr *)old, half, (const Fr *)r, (Fr *)cur, g.stream);
-    DevBuf d_v, d_r;
-    if (d_v.alloc(2 * half * sizeof(Fr)) || d_r.alloc(sizeof(Fr))) { set_error("fr_fold: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    LSA_UPLOAD(d_v.p, old, 2 * half * sizeof(Fr));
-    LSA_UPLOAD(d_r.p, r, sizeof(Fr));
-    rc = fr_fold_halves_device((const Fr *)d_v.p, half, (const Fr *)d_r.p, (Fr *)d_v.p, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    LSA_DOWNLOAD(cur, d_v.p, half * sizeof(Fr));
-    return LSA_OK;
 }
 }  // extern "C"

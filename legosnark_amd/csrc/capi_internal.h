@@ -1,5 +1,6 @@
 // legosnark_amd/csrc/capi_internal.h -- state shared by the translation units that implement the
-// C-ABI (capi.hip: single-GPU entry points; comm.hip: the multi-GPU exchange step).
+// C-ABI (capi.hip: state, bases and the MSM entry points; capi_fr.hip, capi_pairing.hip and the fr_* / point_load units:
+// the other single-GPU entry points; host_copy.hip: the copies below; comm.hip: the multi-GPU exchange step).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -46,31 +47,7 @@ struct CallTrace {
 };
 #define LSA_TRACE_CALL(name, items) CallTrace trace_scope_((name), (size_t)(items))
 void comm_release();               // comm.hip: called by lsa_shutdown
-void pairing_release();            // capi_pairing.hip: staging buffers and the G2 line-table cache
-void fr_poly_release();            // fr_poly.hip: staging buffers of the Lipmaa quotient and the Lagrange row
-void fr_matrix_release();          // fr_matrix.hip: staging buffers of the matrix product and the weighted row / column sums
-void fr_sparse_release();          // fr_sparse.hip: staging buffers of the sparse products and the witness map
-void point_load_release();         // point_load.hip: staging buffers of point decompression, validation and compression
-
-// grow-only device staging buffer of the host-buffer entry points (the libff shim calls them
-// thousands of times with tiny inputs: no hipMalloc / hipFree per call)
-struct StageBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        static const bool noisy = getenv("LSA_TRACE") && getenv("LSA_TRACE")[0] == '2';
-        if (noisy) fprintf(stderr, "[lsa]   stage_grow                  %zu -> %zu bytes\n", cap, bytes < 4096 ? (size_t)4096 : bytes + bytes / 4);
-        if (p) { (void)hipStreamSynchronize(g.stream); (void)hipFree(p); }
-        p = nullptr; cap = 0;
-        size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-        if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return -1; }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-extern StageBuf g_stage_gather;
+void pairing_release();            // capi_pairing.hip: pinned staging, the upload event and the G2 line-table cache
 
 // Pageable host memory <-> device on lsa_stream().  For a large pageable copy hipMemcpy pins the caller's pages in
 // place and keeps the registration; when the caller later frees that vector with munmap (glibc: every allocation above
@@ -94,7 +71,7 @@ int download_host(void *h_dst, const void *d_src, size_t bytes);
 void upload_release();             // threads, pinned slots (lsa_shutdown)
 void upload_prepare();             // the same, created (lsa_init)
 #define LSA_UPLOAD(dst, src, bytes) do { int u_ = upload_host((dst), (src), (bytes)); if (u_) return u_; } while (0)
-#define LSA_DOWNLOAD(dst, src, bytes) do { int u_ = download_host((dst), (src), (bytes)); if (u_) return u_; } while (0)    // all-gather landing zone shared by the sharded MSM and pairing paths
+#define LSA_DOWNLOAD(dst, src, bytes) do { int u_ = download_host((dst), (src), (bytes)); if (u_) return u_; } while (0)
 
 }  // namespace lsa
 
@@ -104,3 +81,5 @@ struct lsa_bases {
     int group = 1;           // 1 = G1, 2 = G2
     size_t table_stride = 0; // n when the pre-shifted window copies 2^(s_k)*P are resident, else 0
 };
+
+#include "staging.h"   // StageBuf, DevBuf, the shared argument checks, OperandFrame

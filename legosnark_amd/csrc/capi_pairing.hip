@@ -547,12 +547,10 @@ int check_segments(const uint64_t *seg, size_t nseg, const char *who) {
 
 namespace lsa {
 void pairing_release() {
-    g_pair_p.release(); g_pair_q.release(); g_pair_f.release(); g_pair_s.release(); g_pair_o.release();
-    g_pair_meta.release(); g_pair_scratch_tabs.release(); g_pair_pub.release();
-    g_pin_meta.release(); g_pin_q.release();
+    g_pin_meta.release(); g_pin_q.release();           // (the StageBufs above: stage_release_all, staging.h)
     if (g_uploaded) { (void)hipEventDestroy(g_uploaded); g_uploaded = nullptr; }
     g_upload_pending = false;
-    g_pending.drop(); g_pending.dev.release();
+    g_pending.drop();
     miller_split_release();
     g_tabs.clear();
 }

@@ -270,22 +270,7 @@ MatvecPlan matvec_plan(size_t rows, size_t cols, int side) {
 
 // grow-only staging (released by lsa_shutdown): the limbs of w, the slices' partial sums, and for host callers the three operands
 StageBuf g_mat_limbs, g_mat_part, g_mat_a, g_mat_b, g_mat_c;
-
-bool bytes_of(size_t n, size_t m, size_t *out) {           // n * m * 32 without overflow
-    size_t e;
-    return !__builtin_mul_overflow(n, m, &e) && !__builtin_mul_overflow(e, sizeof(Fr), out);
-}
-bool overlap(const void *p, size_t np, const void *q, size_t nq) {
-    if (!np || !nq) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + nq && b < a + np;
-}
-bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
 }  // namespace
-
-void fr_matrix_release() {
-    g_mat_limbs.release(); g_mat_part.release(); g_mat_a.release(); g_mat_b.release(); g_mat_c.release();
-}
 
 // All device pointers, 16-byte aligned.  d_limbs: 9 * (side ? cols : rows) words; d_part: slices * outputs elements when the plan
 // has slices.  Asynchronous on st.
@@ -328,7 +313,7 @@ size_t lsa_fr_matrix_param(int which) {
 
 size_t lsa_fr_matvec_slices(size_t rows, size_t cols, int side) {
     size_t bytes;
-    if ((side != 0 && side != 1) || !bytes_of(rows, cols, &bytes)) return 0;
+    if ((side != 0 && side != 1) || !fr_bytes_of(rows, cols, &bytes)) return 0;
     return matvec_plan(rows, cols, side).slices;
 }
 
@@ -338,7 +323,7 @@ int lsa_fr_matvec(const void *m, size_t rows, size_t cols, const void *w, int si
     if (rc) return rc;
     if (side != 0 && side != 1) { set_error("fr_matvec: side %d (0: out[c] = sum_r w[r] M[r][c], 1: out[r] = sum_c M[r][c] w[c])", side); return LSA_ERR_INVALID; }
     size_t m_bytes;
-    if (!bytes_of(rows, cols, &m_bytes)) { set_error("fr_matvec: %zu x %zu elements of 32 bytes overflow size_t", rows, cols); return LSA_ERR_INVALID; }
+    if (!fr_bytes_of(rows, cols, &m_bytes)) { set_error("fr_matvec: %zu x %zu elements of 32 bytes overflow size_t", rows, cols); return LSA_ERR_INVALID; }
     const size_t nout = side ? rows : cols, nsum = side ? cols : rows, out_bytes = nout * sizeof(Fr), w_bytes = nsum * sizeof(Fr);
     if (nout == 0) return LSA_OK;
     if (!out || (m_bytes && !m) || (w_bytes && !w)) { set_error("fr_matvec: null argument"); return LSA_ERR_INVALID; }
@@ -346,18 +331,19 @@ int lsa_fr_matvec(const void *m, size_t rows, size_t cols, const void *w, int si
     if (on_device && (misaligned(m) || misaligned(w) || misaligned(out))) { set_error("fr_matvec: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
     const MatvecPlan p = matvec_plan(rows, cols, side);
     size_t part_bytes = 0;
-    if (p.slices > 1 && !bytes_of(p.slices, nout, &part_bytes)) { set_error("fr_matvec: %zu x %zu partial sums overflow size_t", p.slices, nout); return LSA_ERR_INVALID; }
+    if (p.slices > 1 && !fr_bytes_of(p.slices, nout, &part_bytes)) { set_error("fr_matvec: %zu x %zu partial sums overflow size_t", p.slices, nout); return LSA_ERR_INVALID; }
     size_t limb_bytes;
     if (__builtin_mul_overflow(nsum, 9 * sizeof(uint32_t), &limb_bytes)) { set_error("fr_matvec: the limbs of %zu weights overflow size_t", nsum); return LSA_ERR_INVALID; }
-    if (g_mat_limbs.ensure(limb_bytes) || g_mat_part.ensure(part_bytes) ||
-        (!on_device && (g_mat_a.ensure(m_bytes) || g_mat_b.ensure(w_bytes) || g_mat_c.ensure(out_bytes)))) { set_error("fr_matvec: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (on_device) return fr_matvec_device((const Fr *)m, rows, cols, (const Fr *)w, side, (Fr *)out, (uint32_t *)g_mat_limbs.p, (Fr *)g_mat_part.p, p, g.stream);
-    if (m_bytes) LSA_UPLOAD(g_mat_a.p, m, m_bytes);
-    if (w_bytes) LSA_UPLOAD(g_mat_b.p, w, w_bytes);
-    rc = fr_matvec_device((const Fr *)g_mat_a.p, rows, cols, (const Fr *)g_mat_b.p, side, (Fr *)g_mat_c.p, (uint32_t *)g_mat_limbs.p, (Fr *)g_mat_part.p, p, g.stream);
+    OperandFrame f("fr_matvec", on_device);
+    uint32_t *d_limbs = f.scratch<uint32_t>(g_mat_limbs, limb_bytes);
+    Fr *d_part = f.scratch<Fr>(g_mat_part, part_bytes);
+    const Fr *d_m = f.in<Fr>(g_mat_a, m, m_bytes);
+    const Fr *d_w = f.in<Fr>(g_mat_b, w, w_bytes);
+    Fr *d_out = f.out<Fr>(g_mat_c, out, out_bytes);
+    if (f.rc()) return f.rc();
+    rc = fr_matvec_device(d_m, rows, cols, d_w, side, d_out, d_limbs, d_part, p, g.stream);
     if (rc) return rc;
-    LSA_DOWNLOAD(out, g_mat_c.p, out_bytes);
-    return LSA_OK;
+    return f.download();
 }
 
 int lsa_fr_matmul(const void *a, const void *b, size_t rows_a, size_t inner, size_t cols_b, void *c, int on_device) {
@@ -365,7 +351,7 @@ int lsa_fr_matmul(const void *a, const void *b, size_t rows_a, size_t inner, siz
     int rc = require_ready();
     if (rc) return rc;
     size_t a_bytes, b_bytes, c_bytes;
-    if (!bytes_of(rows_a, inner, &a_bytes) || !bytes_of(inner, cols_b, &b_bytes) || !bytes_of(rows_a, cols_b, &c_bytes)) {
+    if (!fr_bytes_of(rows_a, inner, &a_bytes) || !fr_bytes_of(inner, cols_b, &b_bytes) || !fr_bytes_of(rows_a, cols_b, &c_bytes)) {
         set_error("fr_matmul: (%zu x %zu) (%zu x %zu) elements of 32 bytes overflow size_t", rows_a, inner, inner, cols_b);
         return LSA_ERR_INVALID;
     }
@@ -373,12 +359,13 @@ int lsa_fr_matmul(const void *a, const void *b, size_t rows_a, size_t inner, siz
     if (!c || (a_bytes && (!a || !b))) { set_error("fr_matmul: null argument"); return LSA_ERR_INVALID; }
     if (overlap(c, c_bytes, a, a_bytes) || overlap(c, c_bytes, b, b_bytes)) { set_error("fr_matmul: c overlaps an input"); return LSA_ERR_INVALID; }
     if (on_device && (misaligned(a) || misaligned(b) || misaligned(c))) { set_error("fr_matmul: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
-    if (on_device) return fr_matmul_device((const Fr *)a, (const Fr *)b, rows_a, inner, cols_b, (Fr *)c, g.stream);
-    if (g_mat_a.ensure(a_bytes) || g_mat_b.ensure(b_bytes) || g_mat_c.ensure(c_bytes)) { set_error("fr_matmul: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (a_bytes) { LSA_UPLOAD(g_mat_a.p, a, a_bytes); LSA_UPLOAD(g_mat_b.p, b, b_bytes); }
-    rc = fr_matmul_device((const Fr *)g_mat_a.p, (const Fr *)g_mat_b.p, rows_a, inner, cols_b, (Fr *)g_mat_c.p, g.stream);
+    OperandFrame f("fr_matmul", on_device);
+    const Fr *d_a = f.in<Fr>(g_mat_a, a, a_bytes);           // (inner == 0: both inputs are empty and may be null)
+    const Fr *d_b = f.in<Fr>(g_mat_b, b, b_bytes);
+    Fr *d_c = f.out<Fr>(g_mat_c, c, c_bytes);
+    if (f.rc()) return f.rc();
+    rc = fr_matmul_device(d_a, d_b, rows_a, inner, cols_b, d_c, g.stream);
     if (rc) return rc;
-    LSA_DOWNLOAD(c, g_mat_c.p, c_bytes);
-    return LSA_OK;
+    return f.download();
 }
 }  // extern "C"

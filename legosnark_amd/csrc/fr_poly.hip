@@ -71,6 +71,7 @@ namespace {
 // grow-only staging (released by lsa_shutdown): two working vectors, the transforms' second buffer, the step domain's
 // table of Zinv, and for host callers the result
 StageBuf g_poly_b, g_poly_c, g_poly_tmp, g_poly_h, g_poly_ztab;
+// (what g_poly_ztab holds; a released table has cap 0, and lsa_fr_hadamard_quotient drops the key whenever the table is too small)
 struct ZtabKey { bool valid = false; unsigned big_log = 0, small_log = 0; Fr omega, g; } g_ztab_key;
 
 unsigned row_blocks(size_t count) { return (unsigned)(((count + FR_BATCH_INV_RUN - 1) / FR_BATCH_INV_RUN + ROW_BLOCK - 1) / ROW_BLOCK); }
@@ -96,11 +97,6 @@ int check_domain(const char *who, size_t big_log, int small_log) {
     return LSA_OK;
 }
 }  // namespace
-
-void fr_poly_release() {
-    g_poly_b.release(); g_poly_c.release(); g_poly_tmp.release(); g_poly_h.release(); g_poly_ztab.release();
-    g_ztab_key.valid = false;
-}
 
 // d_h: m + 1 elements holding a (n values, the rest zero) on entry and H on return; d_b, d_c: m elements holding b and c,
 // destroyed; d_tmp: the transforms' second buffer.  Asynchronous on st.
@@ -186,13 +182,15 @@ int lsa_fr_hadamard_quotient(const void *a, const void *b, const void *c, size_t
         return LSA_ERR_INVALID;
     }
     const size_t tmp_elems = step ? big : (big_log > NTT_TILE_LOG ? m : 0), period = step ? big >> small_log : 0;
-    if (g_poly_b.ensure(m * sizeof(Fr)) || g_poly_c.ensure(m * sizeof(Fr)) || g_poly_tmp.ensure(tmp_elems * sizeof(Fr)) ||
-        (!on_device && g_poly_h.ensure((m + 1) * sizeof(Fr)))) { set_error("fr_hadamard_quotient: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    if (period * sizeof(Fr) > g_poly_ztab.cap) {
-        g_ztab_key.valid = false;
-        if (g_poly_ztab.ensure(period * sizeof(Fr))) { set_error("fr_hadamard_quotient: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    }
-    Fr *dv[3] = {on_device ? (Fr *)h_out : (Fr *)g_poly_h.p, (Fr *)g_poly_b.p, (Fr *)g_poly_c.p};
+    OperandFrame f("fr_hadamard_quotient", on_device);
+    Fr *d_b = f.scratch<Fr>(g_poly_b, m * sizeof(Fr)), *d_c = f.scratch<Fr>(g_poly_c, m * sizeof(Fr));
+    Fr *d_tmp = f.scratch<Fr>(g_poly_tmp, tmp_elems * sizeof(Fr));
+    Fr *d_h = f.out<Fr>(g_poly_h, h_out, (m + 1) * sizeof(Fr));
+    if (period * sizeof(Fr) > g_poly_ztab.cap) g_ztab_key.valid = false;
+    f.scratch(g_poly_ztab, period * sizeof(Fr));
+    if (f.rc()) return f.rc();
+    // a, b, c into the working vectors, zero-padded to the domain (not operands of the frame: a device caller's are copied too)
+    Fr *dv[3] = {d_h, d_b, d_c};
     const void *src[3] = {a, b, c};
     for (int j = 0; j < 3; j++) {
         if (n) {
@@ -201,11 +199,9 @@ int lsa_fr_hadamard_quotient(const void *a, const void *b, const void *c, size_t
         }
         if (n < m) HIPCHK(hipMemsetAsync(dv[j] + n, 0, (m - n) * sizeof(Fr), g.stream));
     }
-    rc = hadamard_quotient_device(dv[0], dv[1], dv[2], (unsigned)big_log, small_log, w, cg, d, (Fr *)g_poly_tmp.p, g.stream);
+    rc = hadamard_quotient_device(d_h, d_b, d_c, (unsigned)big_log, small_log, w, cg, d, d_tmp, g.stream);
     if (rc) return rc;
-    // (host callers: the download is enqueued behind the kernels, as in lsa_fr_ntt)
-    if (!on_device) LSA_DOWNLOAD(h_out, dv[0], (m + 1) * sizeof(Fr));
-    return LSA_OK;
+    return f.download();              // (host callers: enqueued behind the kernels, as in lsa_fr_ntt)
 }
 
 int lsa_fr_lagrange(size_t big_log, int small_log, const void *omega, const void *t, void *out, int on_device) {
@@ -219,11 +215,11 @@ int lsa_fr_lagrange(size_t big_log, int small_log, const void *omega, const void
     Fr w, tt;
     memcpy(&w, omega, sizeof w);
     memcpy(&tt, t, sizeof tt);
-    if (!on_device && g_poly_h.ensure(m * sizeof(Fr))) { set_error("fr_lagrange: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    Fr *d_out = on_device ? (Fr *)out : (Fr *)g_poly_h.p;
+    OperandFrame f("fr_lagrange", on_device);
+    Fr *d_out = f.out<Fr>(g_poly_h, out, m * sizeof(Fr));
+    if (f.rc()) return f.rc();
     rc = lagrange_device(d_out, (unsigned)big_log, small_log, w, tt, g.stream);
     if (rc) return rc;
-    if (!on_device) LSA_DOWNLOAD(out, d_out, m * sizeof(Fr));
-    return LSA_OK;
+    return f.download();
 }
 }  // extern "C"

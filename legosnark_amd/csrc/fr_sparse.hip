@@ -158,13 +158,6 @@ constexpr size_t SP_MAX_BLOCKS = (size_t)1 << 20;        // (the kernels stride 
 // map a, b, c and for its host callers H
 StageBuf g_sp_part, g_sp_x, g_sp_out, g_sp_abc[3], g_sp_h;
 
-bool sp_overlap(const void *p, size_t np, const void *q, size_t nq) {
-    if (!np || !nq) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + nq && b < a + np;
-}
-bool sp_misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
-
 void sp_free(SpSide &s) {
     for (void *p : s.owned) (void)hipFree(p);
     s.owned.clear();
@@ -244,11 +237,6 @@ int sp_matvec_device(const SpView &v, const Fr *d_x, Fr *d_out, Fr *d_part, hipS
     return LSA_OK;
 }
 }  // namespace
-
-void fr_sparse_release() {
-    g_sp_part.release(); g_sp_x.release(); g_sp_out.release(); g_sp_h.release();
-    for (StageBuf &b : g_sp_abc) b.release();
-}
 
 }  // namespace lsa
 
@@ -363,18 +351,16 @@ int lsa_fr_sparse_matvec(const lsa_fr_sparse *m, const void *x, int side, void *
     const size_t out_bytes = v.rows * sizeof(Fr), x_bytes = v.xlen * sizeof(Fr);
     if (v.rows == 0) return LSA_OK;
     if (!out || (x_bytes && v.nnz && !x)) { set_error("fr_sparse_matvec: null argument"); return LSA_ERR_INVALID; }
-    if (sp_overlap(out, out_bytes, x, x_bytes)) { set_error("fr_sparse_matvec: out overlaps x"); return LSA_ERR_INVALID; }
-    if (on_device && (sp_misaligned(x) || sp_misaligned(out))) { set_error("fr_sparse_matvec: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
-    if (g_sp_part.ensure(v.nchunks * sizeof(Fr)) || (!on_device && (g_sp_x.ensure(x_bytes) || g_sp_out.ensure(out_bytes)))) {
-        set_error("fr_sparse_matvec: hipMalloc failed");
-        return LSA_ERR_NOMEM;
-    }
-    if (on_device) return sp_matvec_device(v, (const Fr *)x, (Fr *)out, (Fr *)g_sp_part.p, g.stream);
-    if (x_bytes && v.nnz) LSA_UPLOAD(g_sp_x.p, x, x_bytes);
-    rc = sp_matvec_device(v, (const Fr *)g_sp_x.p, (Fr *)g_sp_out.p, (Fr *)g_sp_part.p, g.stream);
+    if (overlap(out, out_bytes, x, x_bytes)) { set_error("fr_sparse_matvec: out overlaps x"); return LSA_ERR_INVALID; }
+    if (on_device && (misaligned(x) || misaligned(out))) { set_error("fr_sparse_matvec: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
+    OperandFrame f("fr_sparse_matvec", on_device);
+    Fr *d_part = f.scratch<Fr>(g_sp_part, v.nchunks * sizeof(Fr));
+    const Fr *d_x = f.in<Fr>(g_sp_x, x, v.nnz ? x_bytes : 0, x_bytes);       // (a matrix without entries reads no x: it may be null)
+    Fr *d_out = f.out<Fr>(g_sp_out, out, out_bytes);
+    if (f.rc()) return f.rc();
+    rc = sp_matvec_device(v, d_x, d_out, d_part, g.stream);
     if (rc) return rc;
-    LSA_DOWNLOAD(out, g_sp_out.p, out_bytes);
-    return LSA_OK;
+    return f.download();
 }
 
 int lsa_fr_qap_witness(const lsa_fr_sparse *A, const lsa_fr_sparse *B, const lsa_fr_sparse *C, const void *z, size_t big_log, int small_log,
@@ -398,27 +384,24 @@ int lsa_fr_qap_witness(const lsa_fr_sparse *A, const lsa_fr_sparse *B, const lsa
     const size_t points = ((size_t)1 << big_log) + (small_log >= 0 ? (size_t)1 << small_log : 0);
     if (n > points) { set_error("fr_qap_witness: %zu constraints on a domain of m = %zu points", n, points); return LSA_ERR_INVALID; }
     const size_t z_bytes = nvars * sizeof(Fr), h_bytes = (points + 1) * sizeof(Fr);
-    if (sp_overlap(h_out, h_bytes, z, z_bytes)) { set_error("fr_qap_witness: h_out overlaps z"); return LSA_ERR_INVALID; }
-    if (on_device && (sp_misaligned(z) || sp_misaligned(h_out))) { set_error("fr_qap_witness: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
+    if (overlap(h_out, h_bytes, z, z_bytes)) { set_error("fr_qap_witness: h_out overlaps z"); return LSA_ERR_INVALID; }
+    if (on_device && (misaligned(z) || misaligned(h_out))) { set_error("fr_qap_witness: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
     const lsa_fr_sparse *mats[3] = {A, B, C};
     size_t chunks = 0;
     for (const lsa_fr_sparse *m : mats) chunks = m->side[1].v.nchunks > chunks ? m->side[1].v.nchunks : chunks;
-    bool nomem = g_sp_part.ensure(chunks * sizeof(Fr)) || (!on_device && (g_sp_x.ensure(z_bytes) || g_sp_h.ensure(h_bytes)));
-    for (StageBuf &b : g_sp_abc) nomem = nomem || b.ensure((n ? n : 1) * sizeof(Fr));     // (never null: n == 0 passes them on unread)
-    if (nomem) { set_error("fr_qap_witness: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    const Fr *d_z = (const Fr *)z;
-    if (!on_device) {
-        if (z_bytes) LSA_UPLOAD(g_sp_x.p, z, z_bytes);
-        d_z = (const Fr *)g_sp_x.p;
-    }
+    OperandFrame f("fr_qap_witness", on_device);
+    Fr *d_part = f.scratch<Fr>(g_sp_part, chunks * sizeof(Fr));
+    const Fr *d_z = f.in<Fr>(g_sp_x, z, z_bytes);
+    void *d_h = f.out(g_sp_h, h_out, h_bytes);
+    Fr *d_abc[3];
+    for (int j = 0; j < 3; j++) d_abc[j] = f.scratch<Fr>(g_sp_abc[j], (n ? n : 1) * sizeof(Fr));     // (never null: n == 0 passes them on unread)
+    if (f.rc()) return f.rc();
     for (int j = 0; j < 3; j++) {
-        rc = sp_matvec_device(mats[j]->side[1].v, d_z, (Fr *)g_sp_abc[j].p, (Fr *)g_sp_part.p, g.stream);
+        rc = sp_matvec_device(mats[j]->side[1].v, d_z, d_abc[j], d_part, g.stream);
         if (rc) return rc;
     }
-    void *d_h = on_device ? h_out : g_sp_h.p;
-    rc = lsa_fr_hadamard_quotient(g_sp_abc[0].p, g_sp_abc[1].p, g_sp_abc[2].p, n, big_log, small_log, omega, coset_g, d123, d_h, 1);
+    rc = lsa_fr_hadamard_quotient(d_abc[0], d_abc[1], d_abc[2], n, big_log, small_log, omega, coset_g, d123, d_h, 1);
     if (rc) return rc;
-    if (!on_device) LSA_DOWNLOAD(h_out, d_h, h_bytes);
-    return LSA_OK;
+    return f.download();
 }
 }  // extern "C"

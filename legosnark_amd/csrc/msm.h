@@ -1,4 +1,4 @@
-// legosnark_amd/csrc/msm.h -- internal interface between the C-ABI (capi.hip) and the
+// legosnark_amd/csrc/msm.h -- internal interface between the C-ABI (capi.hip, capi_fr.hip) and the
 // MSM / normalisation kernels (msm.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -122,14 +122,9 @@ __global__ __launch_bounds__(256) void k_count_rejected(const uint8_t *__restric
 // grow-only staging of the host-buffer calls and the affine form behind lsa_gN_compress (released by lsa_shutdown)
 StageBuf g_pl_in, g_pl_flags, g_pl_out, g_pl_status, g_pl_aff, g_pl_count;
 
-bool overlap(const void *p, size_t np, const void *q, size_t nq) {
-    if (!np || !nq) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + nq && b < a + np;
-}
 // n points of `each` bytes: the byte count fits size_t and the grid fits 2^31 - 1 workgroups
 bool sizes_ok(const char *what, size_t n, size_t each, size_t *bytes) {
-    if (__builtin_mul_overflow(n, each, bytes) || (n + 255) / 256 > 0x7fffffffu) {
+    if (!bytes_of(n, each, bytes) || (n + 255) / 256 > 0x7fffffffu) {
         set_error("%s: %zu points of %zu bytes overflow", what, n, each);
         return false;
     }
@@ -162,26 +157,19 @@ int decompress_any(const char *what, const void *x, const uint8_t *flags, size_t
     if (!x || !flags || !out || !status) { set_error("%s: null argument", what); return LSA_ERR_INVALID; }
     if (overlap(out, out_bytes, x, x_bytes) || overlap(out, out_bytes, flags, n) || overlap(status, n, x, x_bytes) || overlap(status, n, flags, n) ||
         overlap(out, out_bytes, status, n)) { set_error("%s: an output overlaps an input or the other output", what); return LSA_ERR_INVALID; }
-    const F *d_x = (const F *)x;
-    const uint8_t *d_flags = flags;
-    Jac<F> *d_out = (Jac<F> *)out;
-    uint8_t *d_status = status;
-    if (!on_device) {
-        if (g_pl_in.ensure(x_bytes) || g_pl_flags.ensure(n) || g_pl_out.ensure(out_bytes) || g_pl_status.ensure(n)) { set_error("%s: hipMalloc failed", what); return LSA_ERR_NOMEM; }
-        LSA_UPLOAD(g_pl_in.p, x, x_bytes);
-        LSA_UPLOAD(g_pl_flags.p, flags, n);
-        d_x = (const F *)g_pl_in.p; d_flags = (const uint8_t *)g_pl_flags.p; d_out = (Jac<F> *)g_pl_out.p; d_status = (uint8_t *)g_pl_status.p;
-    }
+    OperandFrame f(what, on_device);
+    const F *d_x = f.in<F>(g_pl_in, x, x_bytes);
+    const uint8_t *d_flags = f.in<uint8_t>(g_pl_flags, flags, n);
+    Jac<F> *d_out = f.out<Jac<F>>(g_pl_out, out, out_bytes);
+    uint8_t *d_status = f.out<uint8_t>(g_pl_status, status, n);
+    if (f.rc()) return f.rc();
     hipLaunchKernelGGL((k_decompress<F>), dim3(blocks_of(n)), dim3(256), 0, g.stream, d_x, d_flags, n, d_out, d_status);
     if constexpr (std::is_same<F, Fq2>::value) {
         if (check_subgroup) hipLaunchKernelGGL(k_subgroup_g2, dim3(blocks_of(n)), dim3(256), 0, g.stream, (const Jac<Fq2> *)d_out, n, d_status, d_out);
     }
     HIPCHK(hipGetLastError());
     if (n_rejected) { rc = count_rejected(d_status, n, n_rejected); if (rc) return rc; }
-    if (on_device) return LSA_OK;
-    LSA_DOWNLOAD(out, d_out, out_bytes);
-    LSA_DOWNLOAD(status, d_status, n);
-    return LSA_OK;
+    return f.download();
 }
 
 template <class F>
@@ -194,22 +182,17 @@ int validate_any(const char *what, const void *pts, size_t n, int check_subgroup
     if (n == 0) { if (n_rejected) *n_rejected = 0; return LSA_OK; }
     if (!pts || !status) { set_error("%s: null argument", what); return LSA_ERR_INVALID; }
     if (overlap(status, n, pts, in_bytes)) { set_error("%s: status overlaps the points", what); return LSA_ERR_INVALID; }
-    const Jac<F> *d_pts = (const Jac<F> *)pts;
-    uint8_t *d_status = status;
-    if (!on_device) {
-        if (g_pl_out.ensure(in_bytes) || g_pl_status.ensure(n)) { set_error("%s: hipMalloc failed", what); return LSA_ERR_NOMEM; }
-        LSA_UPLOAD(g_pl_out.p, pts, in_bytes);
-        d_pts = (const Jac<F> *)g_pl_out.p; d_status = (uint8_t *)g_pl_status.p;
-    }
+    OperandFrame f(what, on_device);
+    const Jac<F> *d_pts = f.in<Jac<F>>(g_pl_out, pts, in_bytes);
+    uint8_t *d_status = f.out<uint8_t>(g_pl_status, status, n);
+    if (f.rc()) return f.rc();
     hipLaunchKernelGGL((k_validate<F>), dim3(blocks_of(n)), dim3(256), 0, g.stream, d_pts, n, d_status);
     if constexpr (std::is_same<F, Fq2>::value) {
         if (check_subgroup) hipLaunchKernelGGL(k_subgroup_g2, dim3(blocks_of(n)), dim3(256), 0, g.stream, d_pts, n, d_status, (Jac<Fq2> *)nullptr);
     }
     HIPCHK(hipGetLastError());
     if (n_rejected) { rc = count_rejected(d_status, n, n_rejected); if (rc) return rc; }
-    if (on_device) return LSA_OK;
-    LSA_DOWNLOAD(status, d_status, n);
-    return LSA_OK;
+    return f.download();
 }
 
 template <class F>
@@ -225,30 +208,20 @@ int compress_any(const char *what, const void *pts, size_t n, void *x, uint8_t *
         set_error("%s: an output overlaps the points or the other output", what);
         return LSA_ERR_INVALID;
     }
-    const Jac<F> *d_pts = (const Jac<F> *)pts;
-    F *d_x = (F *)x;
-    uint8_t *d_flags = flags;
-    if (g_pl_aff.ensure(aff_bytes)) { set_error("%s: hipMalloc failed", what); return LSA_ERR_NOMEM; }
-    if (!on_device) {
-        if (g_pl_out.ensure(in_bytes) || g_pl_in.ensure(x_bytes) || g_pl_flags.ensure(n)) { set_error("%s: hipMalloc failed", what); return LSA_ERR_NOMEM; }
-        LSA_UPLOAD(g_pl_out.p, pts, in_bytes);
-        d_pts = (const Jac<F> *)g_pl_out.p; d_x = (F *)g_pl_in.p; d_flags = (uint8_t *)g_pl_flags.p;
-    }
-    rc = normalize_to_affine<F>(d_pts, (Aff<F> *)g_pl_aff.p, n, g.stream);
+    OperandFrame f(what, on_device);
+    Aff<F> *d_aff = f.scratch<Aff<F>>(g_pl_aff, aff_bytes);
+    const Jac<F> *d_pts = f.in<Jac<F>>(g_pl_out, pts, in_bytes);
+    F *d_x = f.out<F>(g_pl_in, x, x_bytes);
+    uint8_t *d_flags = f.out<uint8_t>(g_pl_flags, flags, n);
+    if (f.rc()) return f.rc();
+    rc = normalize_to_affine<F>(d_pts, d_aff, n, g.stream);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_compress<F>), dim3(blocks_of(n)), dim3(256), 0, g.stream, (const Aff<F> *)g_pl_aff.p, n, d_x, d_flags);
+    hipLaunchKernelGGL((k_compress<F>), dim3(blocks_of(n)), dim3(256), 0, g.stream, (const Aff<F> *)d_aff, n, d_x, d_flags);
     HIPCHK(hipGetLastError());
-    if (on_device) return LSA_OK;
-    LSA_DOWNLOAD(x, d_x, x_bytes);
-    LSA_DOWNLOAD(flags, d_flags, n);
-    return LSA_OK;
+    return f.download();
 }
 
 }  // namespace
-
-void point_load_release() {
-    g_pl_in.release(); g_pl_flags.release(); g_pl_out.release(); g_pl_status.release(); g_pl_aff.release(); g_pl_count.release();
-}
 
 }  // namespace lsa
 

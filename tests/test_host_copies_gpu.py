@@ -1,4 +1,4 @@
-"""GPU: host <-> device copies of caller buffers (csrc/capi.hip, upload_host / download_host).  By default copies of
+"""GPU: host <-> device copies of caller buffers (csrc/host_copy.hip, upload_host / download_host).  By default copies of
 32 KiB .. 16 MiB go through pinned slots owned by the library (several threads from two slots up), larger ones are left
 to the runtime; LSA_H2D=staged / direct force one way for every size.  The switch is read once per process, so each
 variant runs in its own interpreter on the same seeded inputs: the same MSM point (multi-slot upload), the same
