@@ -368,6 +368,48 @@ int lsa_fr_hadamard_quotient(const void *a_mont, const void *b_mont, const void 
  * on_device != 0: out is a device pointer and the call is asynchronous on lsa_stream(); else a host pointer, blocking. */
 int lsa_fr_lagrange(size_t big_log, int small_log, const void *omega_mont, const void *t_mont, void *out_mont, int on_device);
 
+/* ---- element-wise algebra on Fr vectors: what a prover or key generator does between the calls above ----------------- */
+/* Common to the five calls below.  Vectors are libff Montgomery words, 32 bytes each; any 256-bit word pattern, in a vector or
+ * in a one-element argument, counts as its value mod r (no canonicalising step on load is needed for the products and sums:
+ * the limb arithmetic of csrc/fr29.h takes any 256-bit pattern; lsa_fr_batch_inverse alone canonicalises every element,
+ * because its zero test and its prefix chain need the canonical value).  Outputs are always canonical (< r): the bytes of the
+ * reference's host loop.  The one-element arguments (scale, coeffs, base, first, x) are HOST pointers in both modes.
+ * on_device != 0: the vector pointers are device pointers, 16-byte aligned, and the call is asynchronous on lsa_stream() with no
+ * host synchronisation inside (any staging is grow-only and owned by the library: only the first call of a larger size waits
+ * for the device).  Else host pointers and a blocking call.  n == 0 is LSA_OK without a launch.  An output vector may be
+ * EXACTLY an input (out == a: in place; every GPU lane reads what it owns before it writes it); any other overlap is refused.
+ * LSA_ERR_INVALID, before any device work: a null pointer with n > 0, a partial overlap, a misaligned device pointer, n * 32
+ * overflowing size_t or n above 2^40, and the limits stated per call. */
+/* out[i] = scale * a[i] * b[i]; scale == NULL: 1.  a == b is legal (squares).  The Hadamard witness c = a o b of
+ * src/gadgets/hadamard.cc:130-135.  Two limb products per element (the second brings libff's form back and carries the scale). */
+int lsa_fr_vec_mul(const void *a_mont, const void *b_mont, const void *scale_mont, size_t n, void *out_mont, int on_device);
+/* out[i] = sum_{t<k} coeffs[t] * xs[t][i], 1 <= k <= LSA_FR_VEC_PARAM_LINCOMB_MAX (8).  xs: HOST array of k vector pointers (as
+ * `tables` of lsa_fr_sumcheck_round); the same vector may appear twice; coeffs: k Fr.  Covers scale (mulByGamma, lipmaa.h:50-52),
+ * add, sub (coefficients 1, r - 1), axpy, and the Groth16 key scalars (beta At + alpha Bt + Ct) / delta in one pass.  Four
+ * products share one Montgomery reduction (csrc/fr_dot.h). */
+int lsa_fr_vec_lincomb(const void *const *xs, const void *coeffs_mont, size_t k, size_t n, void *out_mont, int on_device);
+/* out[i] = first * base^i, i < n; first == NULL: 1.  0^0 = 1.  The chiPows loop of lipmaa.h:98-102 is (base = chi, first = chi)
+ * or (first = NULL, n = m + 1).  Runs of LSA_FR_VEC_PARAM_POWERS_RUN elements, one per GPU lane, each from its own starting power:
+ * no chain across lanes. */
+int lsa_fr_powers(const void *base_mont, const void *first_mont, size_t n, void *out_mont, int on_device);
+/* out[i] = 1 / x[i]; an element that is 0 mod r (the words of 0, r, 2r, ... included) gives 0.  n_zero: HOST, may be NULL; receives
+ * the number of such elements; in device mode a non-null n_zero makes the call blocking (as n_rejected of lsa_g1_decompress).
+ * Runs of LSA_FR_VEC_PARAM_INV_RUN elements with one field inversion each (csrc/fr_batch_inv.h). */
+int lsa_fr_batch_inverse(const void *x_mont, size_t n, void *out_mont, uint64_t *n_zero, int on_device);
+/* out = sum_{i<n} coeffs[i] x^i (one Fr; 0 for n == 0; out must not overlap coeffs): PolyT::eval (polytools.h:92-100),
+ * check_correctness (lipmaa.cc:43-58).  A GPU lane takes LSA_FR_VEC_PARAM_EVAL_ITEMS consecutive coefficients by Horner's rule;
+ * workgroup sums, then a finishing kernel: no atomics on field elements, the same bytes whatever the order. */
+int lsa_fr_poly_eval(const void *coeffs_mont, size_t n, const void *x_mont, void *out_mont, int on_device);
+/* Test and tool support, like lsa_fr_matrix_param: the compiled shape of the five calls.  0 for an unknown selector. */
+#define LSA_FR_VEC_PARAM_LINCOMB_MAX 0   /* -> vectors per lsa_fr_vec_lincomb call at most */
+#define LSA_FR_VEC_PARAM_INV_RUN 1       /* -> elements per lane and inversion of lsa_fr_batch_inverse */
+#define LSA_FR_VEC_PARAM_POWERS_RUN 2    /* -> elements per lane of lsa_fr_powers */
+#define LSA_FR_VEC_PARAM_EVAL_ITEMS 3    /* -> coefficients per lane of lsa_fr_poly_eval */
+#define LSA_FR_VEC_PARAM_PASS_ELEMS 4    /* -> elements one trip of the streaming kernels' grid-stride loop covers on the current device
+                                          *    (grid x block x unroll; 0 before lsa_init) */
+#define LSA_FR_VEC_PARAM_EVAL_BLOCK 5    /* -> coefficients per workgroup (and block partial) of lsa_fr_poly_eval */
+size_t lsa_fr_vec_param(int which);
+
 /* ---- Fr vectors as row-major matrices: the matrix-product gadget (CPMat / CPmmp, src/examples/matrixsc.cc) ---------- */
 /* Weighted sums of the rows or of the columns of a rows x cols matrix M (row-major, M[r * cols + c]):
  *   side 0: out[c] = sum_r w[r] * M[r * cols + c]   (cols results; w has rows entries)

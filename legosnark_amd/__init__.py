@@ -116,6 +116,13 @@ def lib():
         L.lsa_g2_validate.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         for name in ("lsa_g1_compress", "lsa_g2_compress"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+        L.lsa_fr_vec_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+        L.lsa_fr_vec_lincomb.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]
+        L.lsa_fr_powers.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+        L.lsa_fr_batch_inverse.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.lsa_fr_poly_eval.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+        L.lsa_fr_vec_param.argtypes = [C.c_int]
+        L.lsa_fr_vec_param.restype = C.c_size_t
         L.lsa_fr_matvec.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.lsa_fr_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]
         L.lsa_fr_matrix_param.argtypes = [C.c_int]
@@ -866,6 +873,116 @@ def fr_lagrange(big_log, small_log, omega, t, out=None):
     _after_torch(out)
     _check(lib().lsa_fr_lagrange(big_log, sl, _host_ptr(omega), _host_ptr(t), _ptr(out), 1))
     return out
+
+
+def fr_vec_params():
+    """The compiled shape of the element-wise Fr vector calls (lsa_fr_vec_param): the vectors one fr_vec_lincomb takes, the
+    elements per lane of fr_batch_inverse and fr_powers, the coefficients per lane and per workgroup of fr_poly_eval, and the
+    elements one trip of the streaming kernels' loop covers on the current device (pass_elems; 0 before init)."""
+    names = ("lincomb_max", "inv_run", "powers_run", "eval_items", "pass_elems", "eval_block")
+    return {name: int(lib().lsa_fr_vec_param(i)) for i, name in enumerate(names)}
+
+
+def _fr_scalar(name, s):
+    """One Fr for a host-pointer argument: None stays None."""
+    if s is None:
+        return None
+    s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1)
+    if s.size != 4:
+        raise ValueError("%s: a scalar is one Fr (4 words)" % name)
+    return s
+
+
+def _fr_vec_call(name, ins, nout, out, call):
+    """The frame of the element-wise calls: `ins` all numpy (host, blocking) or all torch CUDA tensors (device, asynchronous on
+    the library's stream).  out: None for a new array / tensor of nout entries, or one of the right kind and length -- it may
+    be one of `ins` (in place).  call(pointers of ins, pointer of out, on_device)."""
+    host = all(isinstance(x, np.ndarray) for x in ins) and (bool(ins) or out is None or isinstance(out, np.ndarray))
+    if not host and any(isinstance(x, np.ndarray) for x in ins):
+        raise ValueError("%s: operands must be all numpy arrays or all torch CUDA tensors" % name)
+    if host:
+        ins = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in ins]
+        if out is None:
+            out = np.zeros((nout, 4), dtype=np.uint64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags["C_CONTIGUOUS"] and out.size == 4 * nout):
+            raise ValueError("%s: out must be a contiguous uint64 array of %d entries" % (name, nout))
+        call([_host_ptr(x) for x in ins], _host_ptr(out), 0)
+        return out
+    if out is None:
+        import torch
+        out = torch.empty((nout, 4), dtype=torch.int64, device=ins[0].device if ins else "cuda")
+    elif isinstance(out, np.ndarray) or _fr_vec_len(out) != nout:
+        raise ValueError("%s: out must be a torch CUDA tensor of %d entries" % (name, nout))
+    _after_torch(*ins, out)
+    call([_ptr(x) for x in ins], _ptr(out), 1)
+    return out
+
+
+def _fr_vec_common_len(name, xs):
+    ns = [len(np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4)) if isinstance(x, np.ndarray) else _fr_vec_len(x) for x in xs]
+    if any(n != ns[0] for n in ns):
+        raise ValueError("%s: the vectors must have the same length (got %s)" % (name, ns))
+    return ns[0]
+
+
+def fr_vec_mul(a, b, scale=None, out=None):
+    """out[i] = scale * a[i] * b[i] over Fr (scale None: 1; b may be a): the Hadamard witness c = a o b.  numpy in -> a numpy
+    array; torch CUDA tensors in -> a torch CUDA tensor, asynchronous on the library's stream.  out may be a or b (in place)."""
+    n = _fr_vec_common_len("fr_vec_mul", [a, b])
+    s = _fr_scalar("fr_vec_mul", scale)
+    sp = None if s is None else _host_ptr(s)
+    ins = [a] if b is a else [a, b]
+    return _fr_vec_call("fr_vec_mul", ins, n, out, lambda p, o, dev: _check(lib().lsa_fr_vec_mul(p[0], p[-1], sp, n, o, dev)))
+
+
+def fr_vec_lincomb(xs, coeffs, out=None):
+    """out[i] = sum_t coeffs[t] * xs[t][i] over Fr for 1 .. fr_vec_params()["lincomb_max"] vectors (the same one may appear
+    twice): scaling, sums, differences, and the Groth16 key scalars (beta At + alpha Bt + Ct) / delta in one pass.  coeffs:
+    host words, one Fr per vector.  Modes and `out` as for fr_vec_mul."""
+    xs = list(xs)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+    if len(coeffs) != len(xs):
+        raise ValueError("fr_vec_lincomb: %d vectors, %d coefficients" % (len(xs), len(coeffs)))
+    if not xs:
+        _check(lib().lsa_fr_vec_lincomb(None, _host_ptr(coeffs), 0, 0, None, 0))     # (refused by the library: k = 0)
+    n = _fr_vec_common_len("fr_vec_lincomb", xs)
+    k = len(xs)
+
+    def call(p, o, dev):
+        arr = (C.c_void_p * k)(*[q.value if isinstance(q, C.c_void_p) else q for q in p])
+        _check(lib().lsa_fr_vec_lincomb(arr, _host_ptr(coeffs), k, n, o, dev))
+    return _fr_vec_call("fr_vec_lincomb", xs, n, out, call)
+
+
+def fr_powers(base, n, first=None, out=None):
+    """out[i] = first * base^i, i < n (first None: 1; 0^0 = 1): the chiPows loop of the Lipmaa key generator.  base, first: host
+    words.  out None: a new numpy array (blocking); a torch CUDA tensor `out` of n entries is filled asynchronously on the
+    library's stream."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("fr_powers: negative length")
+    b = _fr_scalar("fr_powers", base)
+    f = _fr_scalar("fr_powers", first)
+    fp = None if f is None else _host_ptr(f)
+    return _fr_vec_call("fr_powers", [], n, out, lambda p, o, dev: _check(lib().lsa_fr_powers(_host_ptr(b), fp, n, o, dev)))
+
+
+def fr_batch_inverse(x, out=None, count_zeros=False):
+    """out[i] = 1 / x[i] over Fr; an element that is 0 mod r gives 0.  count_zeros: also return the number of such elements (in
+    device mode this makes the call blocking).  Modes and `out` (which may be x) as for fr_vec_mul."""
+    n = _fr_vec_common_len("fr_batch_inverse", [x])
+    nz = C.c_uint64(0)
+    res = _fr_vec_call("fr_batch_inverse", [x], n, out,
+                       lambda p, o, dev: _check(lib().lsa_fr_batch_inverse(p[0], n, o, C.byref(nz) if count_zeros else None, dev)))
+    return (res, int(nz.value)) if count_zeros else res
+
+
+def fr_poly_eval(coeffs, x, out=None):
+    """sum_i coeffs[i] x^i over Fr (PolyT::eval): one Fr, (1, 4) words; 0 for no coefficients.  x: host words.  numpy coeffs ->
+    a numpy array; a torch CUDA tensor -> a torch CUDA tensor (`out`, or a new one), asynchronous on the library's stream."""
+    n = _fr_vec_common_len("fr_poly_eval", [coeffs])
+    xs = _fr_scalar("fr_poly_eval", x)
+    return _fr_vec_call("fr_poly_eval", [coeffs], 1, out, lambda p, o, dev: _check(lib().lsa_fr_poly_eval(p[0], n, _host_ptr(xs), o, dev)))
 
 
 def fr_matrix_params():

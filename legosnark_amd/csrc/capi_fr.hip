@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "capi_internal.h"
+#include "fr_elem.h"
 #include "ntt_core.h"
 
 using namespace lsa;
@@ -16,6 +17,33 @@ StageBuf g_stage_ntt_a, g_stage_ntt_tmp;         // lsa_fr_ntt: the data of host
 // (fr_vec.hip) are keyed by these pointers)
 StageBuf g_stage_fr_tmp, g_stage_fr_v, g_stage_fr_r, g_stage_fr_w;
 StageBuf g_stage_sc_partial, g_stage_sc_out;     // lsa_fr_sumcheck_round: block partials and the coefficients (one call per round of a prover)
+// the element-wise calls (fr_elem.hip): for host callers the operands and the result; for every caller the block partials of
+// lsa_fr_poly_eval and the zero counter of lsa_fr_batch_inverse
+StageBuf g_stage_el_x[FR_VEC_LINCOMB_MAX], g_stage_el_out, g_stage_el_partial, g_stage_el_count;
+constexpr size_t FR_VEC_MAX_N = (size_t)1 << 40;   // elements per call: the run kernels' grids stay below 2^31 workgroups
+
+// The checks the element-wise calls share, before any device work: every vector non-null, n * 32 within size_t, n within
+// FR_VEC_MAX_N, device pointers 16-byte aligned, and out either exactly an input (when `in_place` allows it) or apart from it.
+int vec_args(const char *who, const void *const *ins, size_t nin, const void *out, size_t out_elems, size_t n, bool in_place, int on_device, size_t *bytes) {
+    if (!fr_bytes_of(n, 1, bytes) || n > FR_VEC_MAX_N) { set_error("%s: n = %zu exceeds the limit of 2^40 elements per call", who, n); return LSA_ERR_INVALID; }
+    if (!out) { set_error("%s: null argument", who); return LSA_ERR_INVALID; }
+    if (on_device && misaligned(out)) { set_error("%s: device pointers must be 16-byte aligned", who); return LSA_ERR_INVALID; }
+    for (size_t t = 0; t < nin; t++) {
+        if (!ins[t]) { set_error("%s: null argument", who); return LSA_ERR_INVALID; }
+        if (on_device && misaligned(ins[t])) { set_error("%s: device pointers must be 16-byte aligned", who); return LSA_ERR_INVALID; }
+        if (in_place && ins[t] == out) continue;
+        if (overlap(ins[t], *bytes, out, out_elems * sizeof(Fr))) {
+            set_error("%s: out overlaps an input%s", who, in_place ? " without being exactly that input" : "");
+            return LSA_ERR_INVALID;
+        }
+    }
+    return LSA_OK;
+}
+Fr load_fr(const void *p) {
+    Fr x;
+    memcpy(&x, p, sizeof x);
+    return x;
+}
 }  // namespace
 
 // ---------------------------------------------------------------- Fr vectors
@@ -185,5 +213,130 @@ int lsa_fr_fold(const void *old, size_t half, const void *r, void *cur, int on_d
     if (rc) return rc;
     if (!on_device) HIPCHK(hipStreamSynchronize(g.stream));
     return f.download();
+}
+
+// ---------------------------------------------------------------- element-wise vector algebra (fr_elem.hip)
+int lsa_fr_vec_mul(const void *a, const void *b, const void *scale, size_t n, void *out, int on_device) {
+    LSA_TRACE_CALL("fr_vec_mul", n);
+    int rc = require_ready();
+    if (rc) return rc;
+    if (n == 0) return LSA_OK;
+    size_t bytes;
+    const void *ins[2] = {a, b};
+    rc = vec_args("fr_vec_mul", ins, 2, out, n, n, true, on_device, &bytes);
+    if (rc) return rc;
+    Fr s;
+    if (scale) s = load_fr(scale);
+    const Fr c266 = fr_elem_c266(scale ? &s : nullptr);
+    OperandFrame f("fr_vec_mul", on_device);
+    const Fr *d_a = f.in<Fr>(g_stage_el_x[0], a, bytes);
+    const Fr *d_b = (a == b) ? d_a : f.in<Fr>(g_stage_el_x[1], b, bytes);
+    Fr *d_out = f.out<Fr>(g_stage_el_out, out, bytes);
+    if (f.rc()) return f.rc();
+    rc = fr_vec_mul_device(d_a, d_b, c266, n, d_out, g.stream);
+    if (rc) return rc;
+    return f.download();
+}
+
+int lsa_fr_vec_lincomb(const void *const *xs, const void *coeffs, size_t k, size_t n, void *out, int on_device) {
+    LSA_TRACE_CALL("fr_vec_lincomb", n);
+    int rc = require_ready();
+    if (rc) return rc;
+    if (k == 0 || k > FR_VEC_LINCOMB_MAX) { set_error("fr_vec_lincomb: k = %zu not in 1..%u", k, FR_VEC_LINCOMB_MAX); return LSA_ERR_INVALID; }
+    if (n == 0) return LSA_OK;
+    if (!xs || !coeffs) { set_error("fr_vec_lincomb: null argument"); return LSA_ERR_INVALID; }
+    size_t bytes;
+    rc = vec_args("fr_vec_lincomb", xs, k, out, n, n, true, on_device, &bytes);
+    if (rc) return rc;
+    Fr c261[FR_VEC_LINCOMB_MAX];
+    for (size_t t = 0; t < k; t++) c261[t] = fr_elem_c261(load_fr((const char *)coeffs + t * sizeof(Fr)));
+    OperandFrame f("fr_vec_lincomb", on_device);
+    const Fr *d_xs[FR_VEC_LINCOMB_MAX];
+    for (size_t t = 0; t < k; t++) {
+        size_t same = t;                                   // a vector given twice is staged once
+        for (size_t u = 0; u < t; u++) if (xs[u] == xs[t]) { same = u; break; }
+        d_xs[t] = same < t ? d_xs[same] : f.in<Fr>(g_stage_el_x[t], xs[t], bytes);
+    }
+    Fr *d_out = f.out<Fr>(g_stage_el_out, out, bytes);
+    if (f.rc()) return f.rc();
+    rc = fr_vec_lincomb_device(d_xs, c261, k, n, d_out, g.stream);
+    if (rc) return rc;
+    return f.download();
+}
+
+int lsa_fr_powers(const void *base, const void *first, size_t n, void *out, int on_device) {
+    LSA_TRACE_CALL("fr_powers", n);
+    int rc = require_ready();
+    if (rc) return rc;
+    if (n == 0) return LSA_OK;
+    if (!base) { set_error("fr_powers: null argument"); return LSA_ERR_INVALID; }
+    size_t bytes;
+    rc = vec_args("fr_powers", nullptr, 0, out, n, n, false, on_device, &bytes);
+    if (rc) return rc;
+    const Fr base261 = fr_elem_c261(load_fr(base)), f0 = first ? fr_elem_canon(load_fr(first)) : Fr::one();
+    OperandFrame f("fr_powers", on_device);
+    Fr *d_out = f.out<Fr>(g_stage_el_out, out, bytes);
+    if (f.rc()) return f.rc();
+    rc = fr_powers_device(base261, f0, n, d_out, g.stream);
+    if (rc) return rc;
+    return f.download();
+}
+
+int lsa_fr_batch_inverse(const void *x, size_t n, void *out, uint64_t *n_zero, int on_device) {
+    LSA_TRACE_CALL("fr_batch_inverse", n);
+    int rc = require_ready();
+    if (rc) return rc;
+    if (n == 0) { if (n_zero) *n_zero = 0; return LSA_OK; }
+    size_t bytes;
+    rc = vec_args("fr_batch_inverse", &x, 1, out, n, n, true, on_device, &bytes);
+    if (rc) return rc;
+    OperandFrame f("fr_batch_inverse", on_device);
+    unsigned long long *d_zeros = f.scratch<unsigned long long>(g_stage_el_count, sizeof(unsigned long long));
+    const Fr *d_x = f.in<Fr>(g_stage_el_x[0], x, bytes);
+    Fr *d_out = f.out<Fr>(g_stage_el_out, out, bytes);
+    if (f.rc()) return f.rc();
+    rc = fr_batch_inverse_device(d_x, n, d_out, d_zeros, g.stream);
+    if (rc) return rc;
+    rc = f.download();
+    if (rc) return rc;
+    if (n_zero) LSA_DOWNLOAD(n_zero, d_zeros, sizeof(uint64_t));       // (blocking, behind the kernel: device callers too)
+    return LSA_OK;
+}
+
+int lsa_fr_poly_eval(const void *coeffs, size_t n, const void *x, void *out, int on_device) {
+    LSA_TRACE_CALL("fr_poly_eval", n);
+    int rc = require_ready();
+    if (rc) return rc;
+    if (!out || !x) { set_error("fr_poly_eval: null argument"); return LSA_ERR_INVALID; }
+    if (on_device && misaligned(out)) { set_error("fr_poly_eval: device pointers must be 16-byte aligned"); return LSA_ERR_INVALID; }
+    if (n == 0) {                                          // the empty sum
+        if (on_device) HIPCHK(hipMemsetAsync(out, 0, sizeof(Fr), g.stream));
+        else memset(out, 0, sizeof(Fr));
+        return LSA_OK;
+    }
+    size_t bytes;
+    rc = vec_args("fr_poly_eval", &coeffs, 1, out, 1, n, false, on_device, &bytes);
+    if (rc) return rc;
+    const Fr xc = fr_elem_canon(load_fr(x));
+    OperandFrame f("fr_poly_eval", on_device);
+    Fr *d_partial = f.scratch<Fr>(g_stage_el_partial, fr_poly_eval_partials(n) * sizeof(Fr));
+    const Fr *d_c = f.in<Fr>(g_stage_el_x[0], coeffs, bytes);
+    Fr *d_out = f.out<Fr>(g_stage_el_out, out, sizeof(Fr));
+    if (f.rc()) return f.rc();
+    rc = fr_poly_eval_device(d_c, n, xc, d_partial, d_out, g.stream);
+    if (rc) return rc;
+    return f.download();
+}
+
+size_t lsa_fr_vec_param(int which) {
+    switch (which) {
+    case LSA_FR_VEC_PARAM_LINCOMB_MAX: return FR_VEC_LINCOMB_MAX;
+    case LSA_FR_VEC_PARAM_INV_RUN: return FR_ELEM_INV_RUN;
+    case LSA_FR_VEC_PARAM_POWERS_RUN: return FR_ELEM_POWERS_RUN;
+    case LSA_FR_VEC_PARAM_EVAL_ITEMS: return FR_ELEM_EVAL_ITEMS;
+    case LSA_FR_VEC_PARAM_PASS_ELEMS: return g.ready ? fr_elem_pass_elems() : 0;
+    case LSA_FR_VEC_PARAM_EVAL_BLOCK: return fr_poly_eval_block_items();
+    default: return 0;
+    }
 }
 }  // extern "C"

@@ -85,6 +85,15 @@ void fr_vec_release();            // the cached hipGraphs of the recursions (lsa
 int fr_scale_upper_device(const Fr *d_old, size_t half, const Fr &k, Fr *d_cur, hipStream_t st);
 int fr_eq_table_device(const Fr *d_r, size_t d, int variant, Fr *d_tmp, Fr *d_out, hipStream_t st);   // d_tmp: fr_eq_table_scratch_elems(d)
 size_t fr_eq_table_scratch_elems(size_t d);
+// fr_elem.hip: element-wise Fr vector algebra (device pointers, asynchronous on st; the constants as fr_elem.h forms them)
+int fr_vec_mul_device(const Fr *d_a, const Fr *d_b, const Fr &c266, size_t n, Fr *d_out, hipStream_t st);
+int fr_vec_lincomb_device(const Fr *const *d_xs, const Fr *c261, size_t k, size_t n, Fr *d_out, hipStream_t st);
+int fr_powers_device(const Fr &base261, const Fr &first, size_t n, Fr *d_out, hipStream_t st);
+int fr_batch_inverse_device(const Fr *d_x, size_t n, Fr *d_out, unsigned long long *d_zeros, hipStream_t st);
+int fr_poly_eval_device(const Fr *d_c, size_t n, const Fr &x, Fr *d_partial, Fr *d_out, hipStream_t st);   // d_partial: fr_poly_eval_partials(n)
+size_t fr_poly_eval_partials(size_t n);
+size_t fr_poly_eval_block_items();   // coefficients per workgroup of lsa_fr_poly_eval
+size_t fr_elem_pass_elems();         // elements per trip of the streaming kernels' loop on the current device (0: no device)
 
 // ntt.hip: in-place radix-2 NTT of 2^log_n Fr values (device) in at most three passes; d_tmp: 2^log_n scratch elements
 // (unused up to 2^10 points); the twiddle tables are cached per domain (ntt_release frees them)
