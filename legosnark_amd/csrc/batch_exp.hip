@@ -106,15 +106,6 @@ __global__ __launch_bounds__(64) void k_bexp_small(const typename C::Base *__res
     if (lane == 0) out[i] = C::to_jac(acc);
 }
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 unsigned batch_exp_window_bits(size_t n) { return n >= (size_t(1) << 16) ? 12 : 8; }
 
 static void *g_bexp_ws = nullptr;

@@ -18,15 +18,6 @@ struct State {
 };
 extern State g;
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 int require_ready();
 
 // Keyed content fingerprints (NH under a per-process random key, capi.hip): for two distinct inputs of the same

@@ -1,4 +1,4 @@
-// legosnark_amd/csrc/curves.h -- curve traits shared by the MSM pipeline (msm.hip) and the
+// legosnark_amd/csrc/curves.h -- curve traits shared by the MSM pipeline (msm.hip and its stage headers) and the
 // fixed-base batch exponentiation (batch_exp.hip): which representation a group's device
 // kernels compute in, how a device-resident base is stored, and the point operations.
 #pragma once
@@ -30,7 +30,7 @@ struct CurveG1 {
         return g1_madd_head<ENDO>(b0, neg0, endo0, b1, neg1, endo1);
     }
     // PAIRED: the general addition with its products in pairs (fp29.h: xyzz29_add_paired), for the kernels whose registers
-    // allow it -- msm.hip names them through PairedAdd below
+    // allow it -- msm_accumulate.h names them through PairedAdd
     template <bool PAIRED = false>
     static __device__ __forceinline__ Acc add(const Acc &a, const Acc &b) {
         if constexpr (PAIRED) return xyzz29_add_paired(a, b);

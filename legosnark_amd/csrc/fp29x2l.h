@@ -1,5 +1,5 @@
 // legosnark_amd/csrc/fp29x2l.h -- Fq2 with ONE component per lane of a pair (even lane: c0, odd lane: c1), device only:
-// the element type of the two-lane G2 bucket accumulation (msm.hip, k_accumulate_g2_pair).
+// the element type of the two-lane G2 bucket accumulation (msm_accumulate.h, k_accumulate_g2_pair).
 //
 // Why: an XYZZ accumulator over Fq2 is 72 words; with the products' column sums, the prefetched base and the
 // temporaries of a mixed addition one lane needs ~330 registers, so the one-lane kernel runs at two wavefronts per SIMD

@@ -644,15 +644,6 @@ __global__ __launch_bounds__(256) void k_eq_expand(const Fr *__restrict__ LO, co
         out[p] = fr_mul_261(LO[p & mask], fr_to_261(HI[p >> lo]));
 }
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 static unsigned stream_blocks(size_t m) {
     size_t b = (m + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));

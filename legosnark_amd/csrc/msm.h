@@ -1,5 +1,5 @@
 // legosnark_amd/csrc/msm.h -- internal interface between the C-ABI (capi.hip, capi_fr.hip) and the
-// MSM / normalisation kernels (msm.hip).
+// MSM / normalisation pipeline (msm.hip and its stage headers msm_bases.h, msm_sort.h, msm_accumulate.h, msm_reduce.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -11,6 +11,15 @@ namespace lsa {
 
 // printf-style error text retrievable through lsa_last_error()
 void set_error(const char *fmt, ...);
+// a HIP runtime call inside a function that returns an LSA_* status
+#define HIPCHK(x)                                                                      \
+    do {                                                                               \
+        hipError_t e_ = (x);                                                           \
+        if (e_ != hipSuccess) {                                                        \
+            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return LSA_ERR_HIP;                                                        \
+        }                                                                              \
+    } while (0)
 
 // (msm_window_bits: msm_plan.h)
 
@@ -126,21 +135,8 @@ int table_build_g1_device(void *d_table, size_t n, size_t stride, void *d_scratc
 int table_build_g2_device(void *d_table, size_t n, size_t stride, void *d_scratch, hipStream_t st);
 size_t table_build_scratch_bytes(size_t n, int group = 1);
 
-// The tail slots of the MSM pipelines (msm.hip): a call's front runs on the caller's stream, its tail on the slot's
-// internal stream with the slot's workspace; results are ordered again at msm_join().
-struct MsmSlot {
-    hipStream_t tail;     // the slot's stream (the caller's stream itself under LSA_NO_OVERLAP=1)
-    void *ws;             // >= the bytes asked for; owned by this call until its tail has run
-    void *aux;            // 4 KiB that only msm_compact_device uses: zero at creation, left zero by every call
-    int index;
-};
-// picks the next slot, grows its workspace, makes `st` wait for the slot's previous tail
-int msm_slot_begin(hipStream_t st, size_t ws_bytes, const void *d_out, MsmSlot *slot, bool inline_tail = false);
-// the front (on st) is issued: the slot's stream continues from here (and behind any earlier tail that writes d_out)
-int msm_slot_handover(MsmSlot *slot, hipStream_t st);
-// the tail is issued
-int msm_slot_end(MsmSlot *slot, hipStream_t st);
-
+// The tail slots of the MSM pipelines (msm_slots.hip; what the pipelines themselves use of them: msm_slots.h): a call's
+// front runs on the caller's stream, its tail on a slot's internal stream.
 // Orders the results of earlier msm_device calls (whose tails run on an internal stream) on `st`.
 int msm_join(hipStream_t st);
 // Makes `other` wait for them instead and leaves `st` alone.

@@ -25,7 +25,7 @@
 //
 // Chain of one call at n = 4096: ~9 (sort) + ~40 (2 mixed additions + 7 quad additions) + ~35 + ~25 us, against
 // 0.26-0.31 ms on the general pipeline.  Kernel 1 runs on the caller's stream (it is the only reader of the scalars),
-// kernels 2-4 on the call's tail slot (msm.h: msm_slot_*), so consecutive calls overlap like the general pipeline's.
+// kernels 2-4 on the call's tail slot (msm_slots.h: msm_slot_*), so consecutive calls overlap like the general pipeline's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -36,17 +36,10 @@
 #include "fs29.h"
 #include "msm.h"
 #include "msm_plan.h"
+#include "msm_quad.h"
+#include "msm_slots.h"
 
 namespace lsa {
-
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 static constexpr uint32_t CMP_TILE = 256;          // scalars per sort workgroup
 static constexpr uint32_t CMP_MAXB = 1024;         // buckets: 2^(c-1), c = 10 (11 for tables of 6*2^20 points and more)
@@ -112,40 +105,6 @@ __global__ __launch_bounds__(CMP_TILE) void k_cmp_sort(const Fr *__restrict__ sc
     for (uint32_t x = tid; x < total; x += CMP_TILE) e[x] = sorted[x];
     uint16_t *o = toff + (size_t)t * (B + 1);
     for (uint32_t x = tid; x <= B; x += CMP_TILE) o[x] = (uint16_t)off[x];
-}
-
-// ------------------------------------------------------------------------------------ quad helpers
-template <class A>
-__device__ __forceinline__ A cmp_shfl_down(const A &p, unsigned delta) {
-    A r;
-    constexpr int NW = sizeof(A) / 4;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(&p);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&r);
-#pragma unroll
-    for (int w = 0; w < NW; w++) dst[w] = __shfl_down(src[w], delta, 64);
-    return r;
-}
-// the sum of the 16 quads' points, valid in quad 0 (four dependent quad additions; one call site)
-template <class A>
-__device__ __forceinline__ A cmp_quad_tree(A a, unsigned lane, unsigned first_d = 8) {
-    const unsigned sub = lane & 3, qd = lane >> 2;
-#pragma unroll 1
-    for (unsigned d = first_d; d >= 1; d >>= 1) {
-        A o = cmp_shfl_down(a, 4 * d);
-        if (qd + d >= 16) o = A::inf();
-        a = quad_add(a, o, sub);
-    }
-    return a;
-}
-template <class A>
-__device__ __forceinline__ A cmp_load(const A *p) {
-    A r;
-    constexpr int NW = sizeof(A) / 4;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(p);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&r);
-#pragma unroll
-    for (int w = 0; w < NW; w++) dst[w] = src[w];
-    return r;
 }
 
 // ------------------------------------------------------------------------------------ 2: items
@@ -277,7 +236,7 @@ __global__ __launch_bounds__(256) void k_cmp_accumulate(const typename C::Base *
         if (l < used) o = cmp_load(reinterpret_cast<const A *>(&tree_(wv)[l * PITCH]));
         a = quad_add(a, o, sub);
     }
-    a = cmp_quad_tree(a, lane);
+    a = bits_quad_tree(a, lane);
     if (lane == 0) {
         items[item] = a;
         item_w[item] = b + 1;
@@ -305,7 +264,7 @@ __global__ __launch_bounds__(512) void k_cmp_bits(const typename C::Acc *__restr
         if (idx < W && ((item_w[idx] >> bit) & 1u)) o = cmp_load(&items[idx]);
         a = quad_add(a, o, sub);
     }
-    a = cmp_quad_tree(a, lane);
+    a = bits_quad_tree(a, lane);
     if (lane == 0) {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(&a);
 #pragma unroll
@@ -315,7 +274,7 @@ __global__ __launch_bounds__(512) void k_cmp_bits(const typename C::Acc *__restr
     if (wv != 0) return;
     a = A::inf();
     if (qd < 8) a = cmp_load(reinterpret_cast<const A *>(&wave_sum[qd][0]));
-    a = cmp_quad_tree(a, lane, 4);
+    a = bits_quad_tree(a, lane, 4);
 #pragma unroll 1
     for (uint32_t i = 0; i < bit; i++) a = quad_dbl(a, sub);        // weight 2^bit
     if (lane == 0) part[bit * G + g] = a;
@@ -336,7 +295,7 @@ __global__ __launch_bounds__(64) void k_cmp_final(const typename C::Acc *__restr
         if (idx < nparts) o = cmp_load(&part[idx]);
         a = quad_add(a, o, sub);
     }
-    a = cmp_quad_tree(a, lane);
+    a = bits_quad_tree(a, lane);
     if (lane == 0) *out = C::to_jac(a);
 }
 

@@ -61,7 +61,7 @@ inline WidePlan wide_plan_for(size_t n_table, bool big) {
 }
 
 // ------------------------------------------------------------------------------------
-// Sizes the kernels of msm.hip are written for, and what they pass between each other
+// Sizes the kernels of msm.hip (msm_sort.h .. msm_reduce.h) are written for, and what they pass between each other
 // ------------------------------------------------------------------------------------
 #define SORT_TILE 32768u        // plain path: scalars per workgroup of k_rank / k_scatter (u16 ranks)
 #define SCAN_PER_BLOCK 2048     // counters per 256-lane block of the three scan kernels

@@ -31,15 +31,6 @@
 
 namespace lsa {
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 __device__ __forceinline__ Fr fr_pow_dev(Fr base, uint64_t e) {
     Fr acc = Fr::one();
     bool started = false;

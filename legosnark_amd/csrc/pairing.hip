@@ -459,15 +459,6 @@ __global__ __launch_bounds__(192) void k_miller_rtab(const Jac<Fq> *__restrict__
     }
 }
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 // One lane per pairing (miller.h: miller_one): the least total work and no cooperation between lanes -- the fallback of
 // the family (LSA_MILLER_KERNEL=3) beside the fused kernel (k_miller_fused), which every fresh pair takes by default.
 // (Rounds 1-2 also had one pairing per wavefront, six and twelve lanes per pairing -- k_miller_wave / _g6 / _g12; they

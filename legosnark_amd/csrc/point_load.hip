@@ -8,7 +8,7 @@
 //   k_validate<F>     range check, Z == 0, Y^2 == X^3 + b Z^6
 //   k_subgroup_g2     psi(P) == [6u^2]P for the lanes whose status is still LSA_PT_OK (a kernel of its own: launched only when
 //                     the caller asks for the test; 127 doublings + 39 additions over Fq2 per point)
-//   k_compress<F>     from the affine form of msm.hip's batch normalisation: X and the flag byte
+//   k_compress<F>     from the affine form of msm_bases.h's batch normalisation: X and the flag byte
 //   k_count_rejected  statuses >= 2, one atomic per wavefront that holds any
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -79,15 +79,6 @@ __global__ __launch_bounds__(256) void k_col_sum_g2(const Jac<Fq2> *__restrict__
     g2h_store_jac(acc, part, &out[j]);
 }
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return LSA_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 // d_out[i] = d_scalars[d_sidx ? d_sidx[i] : i] * d_pts[i]; d_pts: libff Jacobian, device.
 // Synchronises the stream before returning (temporary buffers are freed).
 int g2_scalar_mul_device(const Jac<Fq2> *d_pts, const Fr *d_scalars, const uint32_t *d_sidx, size_t n, Jac<Fq2> *d_out, hipStream_t st) {

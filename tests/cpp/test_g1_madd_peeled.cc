@@ -2,7 +2,7 @@
 // (xyzz29_madd_signed), the affine + affine head of a bucket list (xyzz29_add_affine), the packed-base wrappers the
 // kernels call (g1_madd_packed / g1_madd_head) and the carry-free subtractions (sub_loose), against xyzz29_madd on an
 // explicitly negated base and against the canonical 32-bit-limb code of ec.h, as field values (X/ZZ, Y/ZZZ).
-// The bucket walk below is the one of msm.hip's accumulate_body.  Build: g++ -std=c++17 -O2 -I legosnark_amd/csrc
+// The bucket walk below is the one of msm_accumulate.h's accumulate_body.  Build: g++ -std=c++17 -O2 -I legosnark_amd/csrc
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -50,7 +50,7 @@ static bool in_bounds(const XYZZ29 &a) {
 }
 
 struct Entry { AffPacked b; bool neg, endo; };
-// the walk of accumulate_body (msm.hip), one lane per bucket
+// the walk of accumulate_body (msm_accumulate.h), one lane per bucket
 template <bool ENDO>
 static XYZZ29 walk_new(const std::vector<Entry> &e) {
     XYZZ29 acc = XYZZ29::inf();

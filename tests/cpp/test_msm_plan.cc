@@ -1,4 +1,4 @@
-// Host unit test of csrc/msm_plan.h: plan_pipeline, the plan of one call of msm.hip's general pipeline.
+// Host unit test of csrc/msm_plan.h: plan_pipeline, the plan of one call of the general pipeline (msm.hip: msm_pipeline; kernels: msm_sort.h .. msm_reduce.h).
 // What keeps the kernels inside their buffers exists nowhere else: the dynamic-LDS requests against the opt-ins of
 // msm_func_attrs, the u16 tile counters, the 30/25-bit point references, k_partition's static arrays, the scratch of the
 // bit-tree reduction, the CoarseMap's tiling of the buckets, and the two workspace layouts.

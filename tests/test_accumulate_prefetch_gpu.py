@@ -1,5 +1,5 @@
 """GPU: the bucket accumulation's loads after the rotation of its loop (k_accumulate<CurveG1, 1 | 2>, k_accumulate_heavy<CurveG1>;
-csrc/msm.hip, "kernel 4").  Iteration j of a lane requests entry word j+2 and the base of entry j+1 unconditionally, on an index
+csrc/msm_accumulate.h, "kernel 4").  Iteration j of a lane requests entry word j+2 and the base of entry j+1 unconditionally, on an index
 clamped to the lane's last entry, and the head of a list requests four words and three bases the same way.  What can go wrong
 is the bookkeeping at the ends of a list: a lane that ends while its neighbours go on, lists shorter than the look-ahead, the
 list at the end of the entries array, an infinity base where the head or the clamp meets it, state carried between calls.

@@ -86,7 +86,7 @@ def test_generator_copies_2pow20(lsa, group):
 @pytest.mark.parametrize("group", ["g1", "g2"])
 def test_pipelined_calls_of_2pow18_pairs_agree_with_blocking_ones(lsa, group):
     """Queued calls above the compact pipeline's range (2^17 pairs) reduce their 2^19 buckets with a lane-private first level
-    (k_reduce2_lane, msm.hip) where a blocking call uses the quad level and the bit trees: both
+    (k_reduce2_lane, msm_reduce.h) where a blocking call uses the quad level and the bit trees: both
     tails on the same inputs, and the known-discrete-log identity on top."""
     import torch
     n = 1 << 18

@@ -1,7 +1,7 @@
 """GPU: the tail slots of the MSM pipelines outside their default mode.
 
-Every MSM runs its tail on one of up to eight slots (csrc/msm.hip: msm_slot_begin, the hand-over, slot_finish); the large
-pipeline and the compact one (msm_compact.hip) share that bookkeeping and differ in when they grow a slot, where they wait
+Every MSM runs its tail on one of up to eight slots (csrc/msm_slots.hip: msm_slot_begin, the hand-over, msm_slot_finish); the large
+pipeline (msm.hip) and the compact one (msm_compact.hip) share that bookkeeping and differ in when they grow a slot, where they wait
 before they publish, and when they move on to the next slot.  LSA_NO_OVERLAP=1 runs every tail on the caller's stream,
 LSA_TAIL_SLOTS=2 makes the slots wrap around after two calls; both are read once per process, so each variant is its own
 interpreter.  Each child queues, without synchronising in between, calls of both pipelines that share destinations and a
