@@ -263,6 +263,43 @@ int lsa_g2_sparse_matrix_msm(const void *vals_jac, const uint32_t *rows, const u
 #define LSA_SMUL_PARAM_G2_LANES_PER_ITEM 4  /* -> lanes that share one G2 item */
 size_t lsa_smul_param(int which);
 
+/* ---- the discrete Fourier transform on group elements ------------------------------------ */
+/* out[k] = sum_{i < n} omega^(ik) * in[i], n = 2^log_n, natural order in and out: lsa_fr_ntt's transform (no coset) with
+ * group elements for data.  inverse != 0: omega^-1 in place of omega, then every out[k] multiplied by n^-1 mod r.
+ * in[i] = a_i * G for all i  =>  out[k] = (lsa_fr_ntt(a))[k] * G.  The inverse transform of a powers string chi^i * G is
+ * the Lagrange-basis key L_i(chi) * G of InterpCommScheme (src/gadgets/lipmaa.h:38-53) without the trapdoor: INTEGRATION.md,
+ * "Lipmaa keys from a powers string (no trapdoor)".
+ *
+ * Points are libff Jacobian (96 B for G1, 192 B for G2; Z == 0: infinity), need not be normalised on input and are valid
+ * representatives, not normalised, on output.  omega: a HOST pointer to one Fr (Montgomery form, as for lsa_fr_ntt) in
+ * both modes.  on_device != 0: in and out are device pointers (16-byte aligned) and the call is asynchronous on
+ * lsa_stream(): no host synchronisation inside, working memory is library-owned and grow-only, so only the first call of
+ * a larger size waits for the device.  Otherwise host pointers, and the call blocks.  out == in exactly is legal (in
+ * place).  log_n == 0 copies the one point.
+ *
+ * LSA_ERR_INVALID, before any device work and before the library is asked for a device: a null pointer; out overlapping in
+ * without being in; log_n > 24; an omega that is not a primitive 2^log_n-th root of unity (omega^(n/2) != -1; omega != 1
+ * for log_n == 0).
+ *
+ * Not checked: that the inputs are on the curve (as for lsa_g1_scalar_mul_batch).  For G2 the twiddles compose mod r, so
+ * the result is the transform only for points of the order-r subgroup -- lsa_g2_validate checks that; points of the twist
+ * outside the subgroup give some point of the twist (every ladder returns the integer multiple) and never a fault.
+ *
+ * Cost: a radix-2 network of log_n stages, each butterfly one 254-bit scalar multiplication and two complete additions.
+ * Stage 1 and every butterfly whose twiddle is 1 run no ladder: (n/2)(log_n - 2) + 1 ladders forward (fewer than
+ * (n/2)(log_n - 1)), n more for the inverse's factor n^-1 (applied to the inputs, one scalar for every lane).
+ *
+ * Out of scope: sizes that are not powers of two (libfqfft's step domain), coset variants, more than one GPU, and the
+ * libff shim (the reference knows its trapdoor: none of its call sites changes). */
+int lsa_g1_ecntt(const void *in_jac, void *out_jac, size_t log_n, const void *omega_mont, int inverse, int on_device);
+int lsa_g2_ecntt(const void *in_jac, void *out_jac, size_t log_n, const void *omega_mont, int inverse, int on_device);
+/* Test and tool support, like lsa_smul_param; 0 for an unknown selector. */
+#define LSA_ECNTT_PARAM_G1_RESIDENT_BUTTERFLIES 0  /* -> butterflies in flight in one pass of the stage kernel's grid, G1 */
+#define LSA_ECNTT_PARAM_G2_RESIDENT_BUTTERFLIES 1  /* -> the same, G2 */
+#define LSA_ECNTT_PARAM_G2_LANES_PER_BUTTERFLY 2   /* -> lanes that share one G2 butterfly */
+#define LSA_ECNTT_PARAM_MAX_LOG_N 3                /* -> the largest log_n the calls accept */
+size_t lsa_ecntt_param(int which);
+
 /* ---- Fr vectors around the MSMs --------------------------------------------------------- */
 /* Witness coefficients of CPPoly::prove (src/gadgets/poly.h:55-67): with v of length 2^d and the
  * evaluation point r of length d, round i = 0..d-1 over m = 2^(d-1-i) pairs writes

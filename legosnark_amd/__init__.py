@@ -102,6 +102,10 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         L.lsa_smul_param.argtypes = [C.c_int]
         L.lsa_smul_param.restype = C.c_size_t
+        for name in ("lsa_g1_ecntt", "lsa_g2_ecntt"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
+        L.lsa_ecntt_param.argtypes = [C.c_int]
+        L.lsa_ecntt_param.restype = C.c_size_t
         L.lsa_fr_cppoly_witness.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_eval_mle.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_fold.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
@@ -684,6 +688,44 @@ def _log2_exact(n):
     if n <= 0 or (1 << d) != n:
         raise ValueError("length must be a power of two")
     return d
+
+
+def ecntt(group, pts, omega, inverse=False, out=None):
+    """The discrete Fourier transform on group elements (lsa_g1_ecntt / lsa_g2_ecntt): out[k] = sum_i omega^(ik) * pts[i]
+    over a power-of-two number of Jacobian points, natural order in and out; inverse: omega^-1 and the factor 1/n.  omega:
+    host Fr (Montgomery words), a primitive n-th root of unity.  numpy in -> numpy out (host, blocking); a torch CUDA tensor
+    in -> a torch CUDA tensor out (device, asynchronous on the library's stream); out may be pts itself (in place)."""
+    w = _group_width(group)
+    omega = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+    fn = lib().lsa_g1_ecntt if group == "g1" else lib().lsa_g2_ecntt
+    if isinstance(pts, np.ndarray):
+        pts = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, w)
+        log_n = _log2_exact(len(pts))
+        if out is None:
+            out = np.zeros_like(pts)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous and out.size == pts.size):
+            raise ValueError("ecntt: out must be a contiguous uint64 array of the input's size")
+        _check(fn(_host_ptr(pts), _host_ptr(out), log_n, _host_ptr(omega), 1 if inverse else 0, 0))
+        return out
+    n = pts.numel() * pts.element_size() // (8 * w)
+    log_n = _log2_exact(n)
+    if out is None:
+        import torch
+        out = torch.empty((n, w), dtype=torch.int64, device=pts.device)
+    elif out.numel() * out.element_size() != n * w * 8:
+        raise ValueError("ecntt: out must hold exactly the input's %d points" % n)
+    _after_torch(pts, out)
+    _check(fn(_ptr(pts), _ptr(out), log_n, _host_ptr(omega), 1 if inverse else 0, 1))
+    return out
+
+
+ECNTT_PARAMS = ("g1_resident_butterflies", "g2_resident_butterflies", "g2_lanes_per_butterfly", "max_log_n")
+
+
+def ecntt_params():
+    """The compiled shape of the group-element transform (lsa_ecntt_param), by name: butterflies in flight in one pass of
+    the stage kernel's grid for each group, lanes per G2 butterfly, the largest log_n.  Answers without a device."""
+    return {name: int(lib().lsa_ecntt_param(i)) for i, name in enumerate(ECNTT_PARAMS)}
 
 
 def cppoly_witness(v, r, out=None):

@@ -79,4 +79,31 @@ __device__ __forceinline__ AffE<F29h> unpack_affine_half(const AffPackedG2 &q, u
     return {{F29::unpack256(q.w[part])}, {F29::unpack256(q.w[2 + part])}};
 }
 
+using XYZZ29h = XyzzE<F29h>;
+
+// this lane's components of a libff Jacobian point as XYZZ: ZZ = Z^2, ZZZ = Z^3
+__device__ __forceinline__ XYZZ29h g2h_from_jac(const Jac<Fq2> &p, unsigned part) {
+    if (p.Z.is_zero()) return XYZZ29h::inf();                          // (the pair reads the same point: uniform)
+    const F29h z = {F29::from_mont256(part ? p.Z.c1 : p.Z.c0)};        // [<2; tight]
+    const F29h zz = sqr<2>(z);                                          // [<2]
+    return {{F29::from_mont256(part ? p.X.c1 : p.X.c0)}, {F29::from_mont256(part ? p.Y.c1 : p.Y.c0)}, zz, mul<2>(zz, z)};   // [<2, <2, <2, <2]
+}
+// XYZZ -> libff Jacobian, this lane's components: Z = ZZZ, X' = X*ZZ^2, Y' = Y*ZZZ^2
+__device__ __forceinline__ void g2h_store_jac(const XYZZ29h &a, unsigned part, Jac<Fq2> *out) {
+    Fq x, y, z;
+    if (a.is_inf()) {
+        const Jac<Fq2> o = Jac<Fq2>::inf();
+        x = part ? o.X.c1 : o.X.c0;
+        y = part ? o.Y.c1 : o.Y.c0;
+        z = part ? o.Z.c1 : o.Z.c0;
+    } else {
+        x = mul<2>(a.X, sqr<2>(a.ZZ)).v.to_mont256();                  // 2*4*2 = 16   [<2]
+        y = mul<2>(a.Y, sqr<2>(a.ZZZ)).v.to_mont256();                 // Y <= 4
+        z = a.ZZZ.v.to_mont256();
+    }
+    (part ? out->X.c1 : out->X.c0) = x;
+    (part ? out->Y.c1 : out->Y.c0) = y;
+    (part ? out->Z.c1 : out->Z.c0) = z;
+}
+
 }  // namespace lsa
