@@ -1,10 +1,12 @@
 // legosnark_amd/csrc/capi_internal.h -- state shared by the translation units that implement the
-// C-ABI (capi.hip: state, bases and the MSM entry points; capi_fr.hip, capi_pairing.hip and the fr_* / point_load units:
-// the other single-GPU entry points; host_copy.hip: the copies below; comm.hip: the multi-GPU exchange step).
+// C-ABI (capi.hip: state, bases and the MSM entry points; crs_cache.hip: the CRS cache behind the host-vector MSMs;
+// capi_fr.hip, capi_pairing.hip and the fr_* / point_load units: the other single-GPU entry points; host_copy.hip: the
+// copies below; comm.hip: the multi-GPU exchange step).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include "keyed_hash.h"
 #include "msm.h"
 
 namespace lsa {
@@ -20,10 +22,11 @@ extern State g;
 
 int require_ready();
 
-// Keyed content fingerprints (NH under a per-process random key, capi.hip): for two distinct inputs of the same
-// length the collision probability over the key is <= 2^-64 (128-bit form), whatever the inputs are.
-void keyed_hash128(const void *bytes, size_t nbytes, uint64_t tweak, uint64_t out[2]);
-uint64_t keyed_hash64(const void *bytes, size_t nbytes, uint64_t tweak);
+// (keyed_hash128 / keyed_hash64, the keyed content fingerprints: keyed_hash.h)
+
+// capi.hip: a handle over n host points of G1 / G2 (group 1 / 2) in the plain layout, never with pre-shifted copies --
+// what the CRS cache inserts (crs_cache.hip)
+int bases_create_plain(const void *bases_jac, size_t n, int group, lsa_bases **out);
 
 // LSA_TRACE=1: one line on stderr per host-facing call -- name, size, wall time (what a caller's profile of the
 // library looks like from outside; off: one predictable branch).

@@ -80,7 +80,7 @@ struct Key128 {
 };
 struct Key128Hash { size_t operator()(const Key128 &k) const { return (size_t)(k.a ^ (k.b * 0x9E3779B97F4A7C15ull)); } };
 
-// 128-bit KEYED fingerprint (capi.hip: NH under a per-process random key): a verifier's results depend on which
+// 128-bit KEYED fingerprint (keyed_hash.h: NH under a per-process random key): a verifier's results depend on which
 // table a point resolves to, so the key of a table must not be something a prover can aim at -- for two distinct
 // points (or blobs) the collision probability over the key is <= 2^-64 whatever their bytes are.
 Key128 fingerprint(const void *bytes, size_t nbytes, uint64_t kind) {

@@ -59,6 +59,9 @@ size_t msm_merge_min();
 bool msm_uses_table(size_t n);    // an MSM of n pairs on a table-carrying handle takes the wide-window pipeline
 void msm_set_merge_min(size_t n);
 bool msm_merge_min_is_explicit();  // lsa_msm_set_table_threshold(n != 0) is in force
+bool msm_precompute_off();         // LSA_PRECOMPUTE=0: no pre-shifted copies anywhere (read from the environment at every call)
+// the warm-up of lsa_init: false with LSA_WARM=0 (everything lazily); *mb = LSA_WARM_MB, the MB of front workspace (400)
+bool msm_warm_mb(size_t *mb);
 // fills windows 1.. of a table whose window 0 holds the n prepared bases
 template <class F>
 int precompute_windows(void *d_table, size_t n, hipStream_t st);

@@ -117,9 +117,14 @@ static int msm_func_attrs() {
 // staging in capi.hip (warm_stage_buffers) -- about 1 GB of the 288 GB per process; LSA_WARM=0 skips all of it (everything
 // is then allocated by the first call that needs it), LSA_WARM_MB sets the size for processes that share a GPU or never see
 // 2^20 pairs (a verifier, a check program: LSA_WARM_MB=16).
+bool msm_warm_mb(size_t *mb) {
+    const char *w = getenv("LSA_WARM"), *m = getenv("LSA_WARM_MB");
+    *mb = m ? (size_t)atoll(m) : 400;
+    return !(w && w[0] == '0');
+}
 int msm_warmup(hipStream_t st) {
-    const char *w = getenv("LSA_WARM");
-    if (w && w[0] == '0') return LSA_OK;
+    size_t warm_mb = 0;
+    if (!msm_warm_mb(&warm_mb)) return LSA_OK;
     int rc = msm_slots_ready();
     if (rc) return rc;
     rc = msm_func_attrs();
@@ -130,8 +135,7 @@ int msm_warmup(hipStream_t st) {
     // more on another (the first G2 MSM of a process: 11.6 ms on a good box with them, 26 ms of them on a slow one).
     // One tail slot: a caller that only ever blocks -- the reference's provers and verifiers -- never leaves slot 0; queued
     // callers grow the other slots on first use.  LSA_WARM_MB=m: front = m MB, tail = 0.9 m (0: nothing).
-    const char *mb = getenv("LSA_WARM_MB");
-    const size_t front = (mb ? (size_t)atoll(mb) : 400) << 20, tailb = front / 10 * 9;
+    const size_t front = warm_mb << 20, tailb = front / 10 * 9;
     if (front) {
         // (no memory: the first call that needs the workspace will say so; LSA_TRACE reports it here)
         if (g_ws.ensure(front) != 0) { (void)hipGetLastError(); if (getenv("LSA_TRACE")) fprintf(stderr, "[lsa]   warm-up: front workspace of %zu MB not allocated\n", front >> 20); }
@@ -257,6 +261,7 @@ size_t msm_merge_min() {
     return g_merge_min;
 }
 bool msm_merge_min_is_explicit() { return g_merge_min_explicit; }
+bool msm_precompute_off() { const char *pe = getenv("LSA_PRECOMPUTE"); return pe && pe[0] == '0'; }
 // whether an MSM of n pairs on a handle that carries the copies runs over them (the wide-window pipeline)
 bool msm_uses_table(size_t n) { return n >= switches().table_use_min; }
 

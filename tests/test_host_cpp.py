@@ -9,13 +9,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name", ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges"])
+@pytest.mark.parametrize("name", ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges", "test_crs_index"])
 def test_host_cpp(name, tmp_path):
     src = os.path.join(ROOT, "tests", "cpp", name + ".cc")
     if not os.path.exists(src):
         pytest.skip(name + " not present")
     exe = str(tmp_path / name)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "legosnark_amd", "csrc"), src, "-o", exe])
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-pthread", "-I", os.path.join(ROOT, "legosnark_amd", "csrc"), src, "-o", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert r.returncode == 0 and "PASS" in r.stdout, r.stdout[-2000:]
 
@@ -66,7 +66,7 @@ def test_host_64_bit_limbs_agree_with_the_device_limbs(tmp_path):
 # an out-of-range index into a limb array) is undefined in the kernels too, where nothing reports it.  Pure host code
 # only: the two programs that link the HIP library (test_shim_io.cc, test_shim_domains.cc) stay out of this tier.
 SANITIZE = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges"]
+_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges", "test_crs_index"]
 _COLS = ["-DLSA_FP29_COLS", "-DLSA_F29_COLS", "-DLSA_FR29_COLS"]
 SANITIZED_PROGRAMS = ([(n, n, []) for n in _HEADER_TESTS]
                       + [(n + "_cols", n, _COLS) for n in ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core", "test_w12_edges"]]
@@ -90,9 +90,25 @@ def test_host_cpp_sanitized(tag, name, defines, tmp_path, sanitizer_toolchain):
     """Every program of this file again with ASan + UBSan, any report fatal: exit status 0 and PASS."""
     src = os.path.join(ROOT, "tests", "cpp", name + ".cc")
     exe = str(tmp_path / (tag + "_san"))
-    subprocess.check_call(["g++", *SANITIZE, *defines, "-I", os.path.join(ROOT, "legosnark_amd", "csrc"), src, "-o", exe])
+    subprocess.check_call(["g++", *SANITIZE, "-pthread", *defines, "-I", os.path.join(ROOT, "legosnark_amd", "csrc"), src, "-o", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0 and "PASS" in r.stdout, r.stdout[-3000:]
+
+
+def test_hash_pool_under_thread_sanitizer(tmp_path):
+    """csrc/hash_pool.h is the library's one piece of hand-written thread code (mutex, condition variables, a generation
+    counter, restarted by lsa_shutdown -> lsa_init): tests/cpp/test_crs_index.cc as a stand-alone program built with
+    ThreadSanitizer reports nothing.  Skips only where a one-line program does not link with -fsanitize=thread."""
+    tsan = ["-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread"]
+    probe = tmp_path / "probe.cc"
+    probe.write_text("int main() { return 0; }\n")
+    r = subprocess.run(["g++", *tsan, str(probe), "-o", str(tmp_path / "probe")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        pytest.skip("g++ cannot link with -fsanitize=thread here: " + r.stdout[-300:])
+    exe = str(tmp_path / "test_crs_index_tsan")
+    subprocess.check_call(["g++", *tsan, "-I", os.path.join(ROOT, "legosnark_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "test_crs_index.cc"), "-o", exe])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0 and "PASS" in r.stdout and "ThreadSanitizer" not in r.stdout, r.stdout[-3000:]
 
 
 def test_oracle_under_ubsan_passes_the_cpu_vector_tests(tmp_path, sanitizer_toolchain):
