@@ -367,6 +367,14 @@ int lsa_fr_ntt(void *a_mont, size_t log_n, const void *omega_mont, int inverse, 
  * <-> values in that order.  omega: a primitive 2^(big_log + 1)-th root of unity (HOST, one Fr: the domain's `omega`,
  * libff::get_root_of_unity(2^(big_log + 1))).  inverse / coset_g / on_device as for lsa_fr_ntt. */
 int lsa_fr_ntt_step(void *a_mont, size_t big_log, size_t small_log, const void *omega_mont, int inverse, const void *coset_g_mont, int on_device);
+/* Test and tool support, like lsa_ecntt_param: the state of the table cache the two calls above (and the quotient and the
+ * witness map through them) share, and the budgets the process runs under.  0 for an unknown selector. */
+#define LSA_FR_NTT_PARAM_RESIDENT_BYTES 0   /* -> bytes of twiddle and coset tables on the device now */
+#define LSA_FR_NTT_PARAM_DOMAIN_TABLES 1    /* -> cached domains (log_n, omega, direction) */
+#define LSA_FR_NTT_PARAM_COSET_TABLES 2     /* -> cached coset generators (log_n, g, direction) */
+#define LSA_FR_NTT_PARAM_CACHE_BUDGET 3     /* -> LSA_NTT_CACHE_MB in bytes */
+#define LSA_FR_NTT_PARAM_T1_BUDGET 4        /* -> LSA_NTT_T1_MB in bytes (the coset powers: a quarter of it) */
+size_t lsa_fr_ntt_param(int which);
 
 /* The Lipmaa Hadamard prover's quotient polynomial (CPHadL::prove, src/gadgets/lipmaa.cc:103-176: coefficients_for_H, the
  * scalar vector of its MSM) from the three committed vectors, all on the device:

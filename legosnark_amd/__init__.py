@@ -111,6 +111,8 @@ def lib():
         L.lsa_fr_fold.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_ntt.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.lsa_fr_ntt_step.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.lsa_fr_ntt_param.argtypes = [C.c_int]
+        L.lsa_fr_ntt_param.restype = C.c_size_t
         L.lsa_fr_hadamard_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int]
         L.lsa_fr_lagrange.argtypes = [C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -858,6 +860,14 @@ def fr_ntt_step(a, big_log, small_log, omega, inverse=False, coset=None):
     _after_torch(a)
     _check(lib().lsa_fr_ntt_step(_ptr(a), big_log, small_log, _host_ptr(omega), 1 if inverse else 0, _host_ptr(cg) if cg is not None else None, 1))
     return a
+
+
+def fr_ntt_params():
+    """The table cache behind fr_ntt / fr_ntt_step / fr_hadamard_quotient / fr_qap_witness (lsa_fr_ntt_param), by name: the
+    bytes of twiddle and coset tables on the device now, the cached domains and coset generators, and the two budgets
+    (LSA_NTT_CACHE_MB, LSA_NTT_T1_MB) in bytes."""
+    names = ("resident_bytes", "domain_tables", "coset_tables", "cache_budget", "t1_budget")
+    return {name: int(lib().lsa_fr_ntt_param(i)) for i, name in enumerate(names)}
 
 
 def _fr_vec_len(x):

@@ -111,6 +111,7 @@ size_t fr_elem_pass_elems();         // elements per trip of the streaming kerne
 // (unused up to 2^10 points); the twiddle tables are cached per domain (ntt_release frees them)
 int fr_ntt_device(Fr *d_a, unsigned log_n, const Fr &omega, bool inverse, const Fr *coset, Fr *d_tmp, hipStream_t st);
 void ntt_release();
+size_t ntt_param(int which);         // lsa_fr_ntt_param: the table cache's state and budgets
 // libfqfft step_radix2_domain (m = 2^big_log + 2^small_log) in place on d_a; d_scratch: 2^big_log elements; omega: primitive
 // 2^(big_log + 1)-th root of unity
 int fr_ntt_step_device(Fr *d_a, unsigned big_log, unsigned small_log, const Fr &omega, bool inverse, const Fr *coset, Fr *d_scratch, hipStream_t st);

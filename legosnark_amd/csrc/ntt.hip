@@ -147,6 +147,11 @@ size_t ntt_cache_budget() {
     static const size_t b = (size_t)(getenv("LSA_NTT_CACHE_MB") ? atol(getenv("LSA_NTT_CACHE_MB")) : 2048) << 20;
     return b;
 }
+// pass 1's twiddles as one table while n * 32 B stays within it; the coset powers up to a quarter of it
+size_t ntt_t1_budget() {
+    static const size_t b = (size_t)(getenv("LSA_NTT_T1_MB") ? atol(getenv("LSA_NTT_T1_MB")) : 512) << 20;
+    return b;
+}
 template <class T> void ntt_drop(T &d) {
     if (d.mem) { (void)hipFree(d.mem); g_ntt_bytes -= d.bytes; }
     d = T();
@@ -184,8 +189,7 @@ int domain_tables(const NttPlan &p, const Fr &omega, bool inverse, hipStream_t s
     const size_t n2t = p.l2 ? (size_t)1 << (p.l2 + p.l3) : 0;
     // pass 1's twiddles as one table of n entries (a product per element less) while n * 32 B stays within LSA_NTT_T1_MB
     // (default 512: up to 2^24 elements); beyond, and for rows shorter than a lane's run, the two-level look-up
-    static const size_t t1_budget = (size_t)(getenv("LSA_NTT_T1_MB") ? atol(getenv("LSA_NTT_T1_MB")) : 512) << 20;
-    const size_t n1t = (p.l1 && p.L - p.l1 >= 4 && (((size_t)1 << p.L) * sizeof(Fr)) <= t1_budget) ? (size_t)1 << p.L : 0;
+    const size_t n1t = (p.l1 && p.L - p.l1 >= 4 && (((size_t)1 << p.L) * sizeof(Fr)) <= ntt_t1_budget()) ? (size_t)1 << p.L : 0;
     const size_t dbytes = (nW + nlo + nhi + n2t + n1t) * sizeof(Fr) + nW * 36;
     ntt_make_room(dbytes, protect);
     if (hipMalloc(&d.mem, dbytes) != hipSuccess) { (void)hipGetLastError(); d.mem = nullptr; set_error("fr_ntt: twiddle allocation failed"); return LSA_ERR_NOMEM; }
@@ -231,7 +235,7 @@ int coset_tables(const NttPlan &p, const Fr &g, bool inverse, hipStream_t st, ui
     // the powers as one table of n entries (a product per element less) up to a quarter of the budget of pass 1's twiddles:
     // 128 MB, 2^22 elements -- at 2^24 the second 512-MB stream costs what the product saved (icosetFFT 2.52 -> 2.54 ms;
     // 2^20: 0.187 -> 0.172)
-    static const size_t full_budget = ((size_t)(getenv("LSA_NTT_T1_MB") ? atol(getenv("LSA_NTT_T1_MB")) : 512) << 20) / 4;
+    const size_t full_budget = ntt_t1_budget() / 4;
     const size_t nfull = (p.L > NTT_TILE_LOG && (((size_t)1 << p.L) * sizeof(Fr)) <= full_budget) ? (size_t)1 << p.L : 0;
     const size_t cbytes = (nlo + nhi + nfull) * sizeof(Fr);
     ntt_make_room(cbytes, protect);
@@ -258,6 +262,17 @@ int coset_tables(const NttPlan &p, const Fr &g, bool inverse, hipStream_t st, ui
 void ntt_release() {
     for (auto &d : g_dom) ntt_drop(d);
     for (auto &d : g_cos) ntt_drop(d);
+}
+size_t ntt_param(int which) {
+    size_t count = 0;
+    switch (which) {
+    case LSA_FR_NTT_PARAM_RESIDENT_BYTES: return g_ntt_bytes;
+    case LSA_FR_NTT_PARAM_DOMAIN_TABLES: for (auto &d : g_dom) count += d.mem != nullptr; return count;
+    case LSA_FR_NTT_PARAM_COSET_TABLES: for (auto &d : g_cos) count += d.mem != nullptr; return count;
+    case LSA_FR_NTT_PARAM_CACHE_BUDGET: return ntt_cache_budget();
+    case LSA_FR_NTT_PARAM_T1_BUDGET: return ntt_t1_budget();
+    }
+    return 0;
 }
 
 // d_a: 2^log_n elements, transformed in place (the result is in d_a when the call returns to the stream); d_tmp: scratch
@@ -460,3 +475,5 @@ int fr_ntt_step_device(Fr *d_a, unsigned big_log, unsigned small_log, const Fr &
 }
 
 }  // namespace lsa
+
+extern "C" size_t lsa_fr_ntt_param(int which) { return lsa::ntt_param(which); }

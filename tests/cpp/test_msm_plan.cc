@@ -231,10 +231,94 @@ static void pinned() {
     CHECK(!plan_pipeline(shape_of(2, (size_t)1 << 20, 1, (size_t)1 << 20), sw).lane_l1_shape, "G2 lane_l1");
 }
 
+// The (shape, switches) pairs of tests/test_switch_paths_gpu.py.  Each variant there sets a switch in order to run a kernel the
+// default plan of that shape does not; which kernel runs is a flag of the plan, so the plan must carry the flag the GPU test
+// means -- with the switch, and not without it.  Handles of n points (table_stride = n), one segment.
+static void switch_paths() {
+    const size_t N16 = (size_t)1 << 16;
+    const MsmSwitches def;
+    const size_t wide_ns[2] = {N16, N16 + 1};
+    char tag[96];
+    // M1: LSA_NO_PART + LSA_NO_REC32 -> k_scatter_wide<1> / k_fine_sort<u64> (64-bit records, 7 fine bits), as n > 2^25 does by default
+    MsmSwitches m1;
+    m1.no_part = true;
+    m1.no_rec32 = true;
+    for (size_t n : wide_ns) {
+        snprintf(tag, sizeof tag, "[M1 n=%zu]", n);
+        const MsmShape sh = shape_of(1, n, 1, n, true);
+        const PipelinePlan p = plan_pipeline(sh, m1), d = plan_pipeline(sh, def);
+        CHECK(p.status == PLAN_OK && d.status == PLAN_OK, "%s status", tag);
+        CHECK(p.wide && p.big && p.fine && !p.part && !p.rec32 && p.fine_bits == WIDE_FINE_BITS, "%s wide %d big %d fine %d part %d rec32 %d", tag, (int)p.wide, (int)p.big, (int)p.fine, (int)p.part, (int)p.rec32);
+        CHECK(p.front.r[F_RECS].bytes >= p.ne * 8, "%s 64-bit records in %zu bytes", tag, p.front.r[F_RECS].bytes);
+        CHECK(d.fine && d.part && d.rec32, "%s default: part %d rec32 %d", tag, (int)d.part, (int)d.rec32);
+        check_plan(sh, p, tag);
+    }
+    {
+        // the plan n > 2^25 takes without any switch is the same one
+        const MsmShape sh = shape_of(1, ((size_t)1 << 25) + 1, 1, ((size_t)1 << 25) + 1);
+        const PipelinePlan p = plan_pipeline(sh, def);
+        CHECK(p.status == PLAN_OK && p.wide && p.big && p.fine && !p.part && !p.rec32, "[n=2^25+1 default] fine %d part %d rec32 %d", (int)p.fine, (int)p.part, (int)p.rec32);
+    }
+    // M3: LSA_NO_REDUCE_BITS -> blocking calls reduce through the 16-ary levels
+    {
+        MsmSwitches m3;
+        m3.no_reduce_bits = true;
+        const MsmShape sh = shape_of(1, N16, 1, N16, true);
+        const PipelinePlan p = plan_pipeline(sh, m3), d = plan_pipeline(sh, def);
+        CHECK(d.status == PLAN_OK && d.bits_tail, "[M3] default bits_tail %d", (int)d.bits_tail);
+        CHECK(p.status == PLAN_OK && !p.bits_tail && p.big && p.wpw == d.wpw, "[M3] bits_tail %d", (int)p.bits_tail);
+        check_plan(sh, p, "[M3]");
+    }
+    // M4: LSA_NO_LANE_L1 -> queued G1 calls keep the quad kernel in the first 16-ary level
+    {
+        MsmSwitches m4;
+        m4.no_lane_l1 = true;
+        const MsmShape sh = shape_of(1, N16, 1, N16, false);
+        const PipelinePlan p = plan_pipeline(sh, m4), d = plan_pipeline(sh, def);
+        CHECK(d.status == PLAN_OK && d.lane_l1_shape, "[M4] default lane_l1 %d", (int)d.lane_l1_shape);
+        CHECK(p.status == PLAN_OK && !p.lane_l1_shape, "[M4] lane_l1 %d", (int)p.lane_l1_shape);
+        check_plan(sh, p, "[M4]");
+    }
+    // M5: LSA_G2_LANE_L1=1 -> k_reduce2_lane<CurveG2> for queued G2 calls
+    {
+        MsmSwitches m5;
+        m5.g2_lane_l1 = true;
+        const MsmShape sh = shape_of(2, N16, 1, N16, false);
+        const PipelinePlan p = plan_pipeline(sh, m5), d = plan_pipeline(sh, def);
+        CHECK(d.status == PLAN_OK && !d.lane_l1_shape, "[M5] default lane_l1 %d", (int)d.lane_l1_shape);
+        CHECK(p.status == PLAN_OK && p.lane_l1_shape && p.big, "[M5] lane_l1 %d", (int)p.lane_l1_shape);
+        CHECK(!plan_pipeline(shape_of(2, N16, 1, N16, true), m5).lane_l1_shape, "[M5] blocking lane_l1");
+        check_plan(sh, p, "[M5]");
+    }
+    // M6a: LSA_WIDE_BIG_MIN=1048576 -> 26 narrow digits at 2^16 pairs and beyond: 512 buckets, every one of them heavy
+    MsmSwitches m6a;
+    m6a.wide_big_min = 1048576;
+    for (size_t n : wide_ns) {
+        snprintf(tag, sizeof tag, "[M6a n=%zu]", n);
+        const MsmShape sh = shape_of(1, n, 1, n, true);
+        const PipelinePlan p = plan_pipeline(sh, m6a), d = plan_pipeline(sh, def);
+        CHECK(d.status == PLAN_OK && d.big && d.nwin == 13, "%s default big %d nwin %u", tag, (int)d.big, d.nwin);
+        CHECK(p.status == PLAN_OK && p.wide && !p.big && p.nwin == 26 && p.heavy_threshold == 4, "%s big %d nwin %u thr %u", tag, (int)p.big, p.nwin, p.heavy_threshold);
+        CHECK(p.ne / p.nb > p.heavy_threshold, "%s %zu entries over %u buckets", tag, p.ne, p.nb);
+        check_plan(sh, p, tag);
+    }
+    // M6b: LSA_WIDE_BIG_MIN=4096 -> 13 wide digits over 2^19 buckets at 4099 pairs
+    {
+        MsmSwitches m6b;
+        m6b.wide_big_min = 4096;
+        const MsmShape sh = shape_of(1, 4099, 1, 4099, true);
+        const PipelinePlan p = plan_pipeline(sh, m6b), d = plan_pipeline(sh, def);
+        CHECK(d.status == PLAN_OK && !d.big && d.nwin == 26, "[M6b] default big %d nwin %u", (int)d.big, d.nwin);
+        CHECK(p.status == PLAN_OK && p.wide && p.big && p.nwin == 13 && p.nb == 1u << 19 && p.ne < p.nb / 8, "[M6b] big %d nwin %u nb %u", (int)p.big, p.nwin, p.nb);
+        check_plan(sh, p, "[M6b]");
+    }
+}
+
 int main() {
     sweep();
     rejections();
     pinned();
+    switch_paths();
     printf("%ld plans checked\n", plans);
     if (fails) { printf("%d FAILURES\n", fails); return 1; }
     printf("PASS\n");
