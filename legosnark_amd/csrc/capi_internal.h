@@ -1,7 +1,8 @@
 // legosnark_amd/csrc/capi_internal.h -- state shared by the translation units that implement the
 // C-ABI (capi.hip: state, bases and the MSM entry points; crs_cache.hip: the CRS cache behind the host-vector MSMs;
-// capi_fr.hip, capi_pairing.hip and the fr_* / point_load units: the other single-GPU entry points; host_copy.hip: the
-// copies below; comm.hip: the multi-GPU exchange step).
+// capi_fr.hip, capi_pairing.hip and the fr_* / point_load units: the other single-GPU entry points -- the pairing unit's
+// host-only rules are pairing_plan.h and g2_table_index.h; host_copy.hip: the copies below; comm.hip: the multi-GPU
+// exchange step).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -10,6 +10,15 @@
 // point, or the precomp blob), and every Miller loop over it runs the Fq12 chain only.  Products share
 // accumulators (f <- f^2 * prod line_i) when there are more pairs than the chip has lanes for.
 // No CPU arithmetic: the host only fingerprints, deduplicates and lays out index arrays.
+//
+// What is a pure function of host data lives in two headers that the host tests compile without HIP:
+//   pairing_plan.h    -- plan_pairing: the route of a job, M, the accumulators and the layout of its pinned index block
+//                        (tests/cpp/test_pairing_plan.cc);
+//   g2_table_index.h  -- the cache's rules: keys, slots, LRU with pinned slots, the call guard, the promises of a
+//                        prefetch (tests/cpp/test_g2_table_index.cc).
+// This file owns the device memory behind the slots, the staging buffers and the order of the launches.
+// (These entry points do not go through OperandFrame, staging.h: their operands are one pinned index block per call and
+// the on_device calls return without synchronising, which a frame of per-operand copies does not express.)
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,6 +27,8 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "g2_table_index.h"
+#include "pairing_plan.h"
 #include "tower.h"
 
 namespace lsa {
@@ -39,64 +50,55 @@ using namespace lsa;
 
 namespace {
 
+static_assert(sizeof(Jac<Fq>) == PAIRING_G1_BYTES, "pairing_plan.h lays out the inline G1 points of a job");
+
 StageBuf g_pair_p, g_pair_q, g_pair_f, g_pair_s, g_pair_o;     // points, Miller values, product scratch, results
 StageBuf g_pair_meta, g_pair_scratch_tabs, g_pair_pub;         // index arrays, uncached tables, public-form staging
 
-// pinned host staging for the small index arrays of a call (one H2D copy)
-struct PinnedBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) { (void)hipStreamSynchronize(g.stream); (void)hipHostFree(p); }
-        p = nullptr; cap = 0;
-        size_t want = bytes < 65536 ? 65536 : bytes + bytes / 4;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return -1; }
-        cap = want;
-        return 0;
+// Pinned host staging for the small arrays of a call (one H2D copy each), and the one rule about it: a pinned block is
+// not rewritten before its copy has run.  An on_device call returns without synchronising, so mark() records an event
+// after the uploads of a call and wait() waits for it before the next call writes.
+struct PinnedStaging {
+    struct Buf {
+        void *p = nullptr;
+        size_t cap = 0;
+        int ensure(size_t bytes) {
+            if (bytes <= cap) return 0;
+            if (p) { (void)hipStreamSynchronize(g.stream); (void)hipHostFree(p); }
+            p = nullptr; cap = 0;
+            size_t want = bytes < 65536 ? 65536 : bytes + bytes / 4;
+            if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return -1; }
+            cap = want;
+            return 0;
+        }
+        void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    };
+    Buf meta, q;                           // the index block of a call; points and destinations of the tables to build
+    hipEvent_t uploaded = nullptr;
+    bool pending = false;
+    int wait() {
+        if (pending) { HIPCHK(hipEventSynchronize(uploaded)); pending = false; }
+        return LSA_OK;
     }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-PinnedBuf g_pin_meta, g_pin_q;
-// the pinned staging of a call must not be rewritten before its copies have run (an on_device call returns
-// without synchronising): recorded after the uploads, waited for at the start of the next call
-hipEvent_t g_uploaded = nullptr;
-bool g_upload_pending = false;
-int wait_uploads() {
-    if (g_upload_pending) { HIPCHK(hipEventSynchronize(g_uploaded)); g_upload_pending = false; }
-    return LSA_OK;
-}
-int mark_uploads() {
-    if (!g_uploaded) HIPCHK(hipEventCreateWithFlags(&g_uploaded, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(g_uploaded, g.stream));
-    g_upload_pending = true;
-    return LSA_OK;
-}
+    int mark() {
+        if (!uploaded) HIPCHK(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(uploaded, g.stream));
+        pending = true;
+        return LSA_OK;
+    }
+    void release() {
+        meta.release(); q.release();
+        if (uploaded) { (void)hipEventDestroy(uploaded); uploaded = nullptr; }
+        pending = false;
+    }
+} g_pin;
 
-// ---------------------------------------------------------------- G2 line-table cache
-struct Key128 {
-    uint64_t a, b;
-    bool operator==(const Key128 &o) const { return a == o.a && b == o.b; }
-};
-struct Key128Hash { size_t operator()(const Key128 &k) const { return (size_t)(k.a ^ (k.b * 0x9E3779B97F4A7C15ull)); } };
-
-// 128-bit KEYED fingerprint (keyed_hash.h: NH under a per-process random key): a verifier's results depend on which
-// table a point resolves to, so the key of a table must not be something a prover can aim at -- for two distinct
-// points (or blobs) the collision probability over the key is <= 2^-64 whatever their bytes are.
-Key128 fingerprint(const void *bytes, size_t nbytes, uint64_t kind) {
-    uint64_t h[2];
-    keyed_hash128(bytes, nbytes, kind, h);
-    return Key128{h[0], h[1]};
-}
-
+// ---------------------------------------------------------------- G2 line-table cache: the device memory behind
+// the slots of g2_table_index.h
 struct TableCache {
     static constexpr size_t BLOCK = 128;                  // tables per device allocation
-    size_t max_tables = 4096;                             // 90 MB; LSA_G2_TABLES / lsa_g2_table_cache
+    G2TableIndex ix;                                      // capacity: LSA_G2_TABLES / lsa_g2_table_cache
     std::vector<void *> blocks;
-    struct Slot { Key128 key; uint64_t tick; bool used; bool pending; };      // pending: promised by a prefetch, not built yet
-    std::vector<Slot> slots;
-    std::unordered_map<Key128, uint32_t, Key128Hash> map;
-    uint64_t tick = 0, hits = 0, misses = 0, evictions = 0;
     uint32_t *ident = nullptr;                            // the table of a pair that is not there
     bool env_read = false;
 
@@ -104,89 +106,45 @@ struct TableCache {
     void read_env() {
         if (env_read) return;
         env_read = true;
-        if (const char *e = getenv("LSA_G2_TABLES")) max_tables = (size_t)strtoull(e, nullptr, 10);
+        if (const char *e = getenv("LSA_G2_TABLES")) ix.set_capacity((size_t)strtoull(e, nullptr, 10));
     }
     int ensure_ident() {
         if (ident) return 0;
         if (hipMalloc((void **)&ident, g2_table_words() * 4) != hipSuccess) { ident = nullptr; return -1; }
         return g2_table_identity_device(ident, g.stream);
     }
-    // slot of `key`, -1 on a miss
-    long lookup(const Key128 &key) {
-        auto it = map.find(key);
-        if (it == map.end()) { misses++; return -1; }
-        hits++;
-        slots[it->second].tick = tick;
-        return (long)it->second;
-    }
-    // a free slot for `key` (a released one, a new one, or the least recently used one that neither a term of the
-    // current call nor an unbuilt promise of an earlier prefetch refers to), -1 if none
+    // ix.insert with memory behind the slot: the block of a slot the index is about to create is allocated BEFORE the key
+    // enters the map, so a failed allocation is a plain miss (-1)
     long insert(const Key128 &key, bool pending = false) {
-        long s = -1;
-        if (!free_slots.empty()) {
-            s = (long)free_slots.back();
-            free_slots.pop_back();
-            slots[(size_t)s] = Slot{key, tick, true, pending};
-        } else if (slots.size() < max_tables) {
-            if (slots.size() == blocks.size() * BLOCK) {
-                void *b = nullptr;
-                if (hipMalloc(&b, BLOCK * g2_table_words() * 4) != hipSuccess) { (void)hipGetLastError(); return -1; }
-                blocks.push_back(b);
-            }
-            slots.push_back(Slot{key, tick, true, pending});
-            s = (long)slots.size() - 1;
-        } else {
-            uint64_t best = tick;
-            for (size_t i = 0; i < slots.size(); i++)
-                if (slots[i].used && !slots[i].pending && slots[i].tick < best) { best = slots[i].tick; s = (long)i; }
-            if (s < 0) return -1;
-            map.erase(slots[(size_t)s].key);
-            evictions++;
-            slots[(size_t)s] = Slot{key, tick, true, pending};
+        if (ix.slot_to_create() == (long)(blocks.size() * BLOCK)) {
+            void *b = nullptr;
+            if (hipMalloc(&b, BLOCK * g2_table_words() * 4) != hipSuccess) { (void)hipGetLastError(); return -1; }
+            blocks.push_back(b);
         }
-        map[key] = (uint32_t)s;
-        return s;
+        return ix.insert(key, pending);
     }
-    // forgets `key` (a table that was promised or begun and never finished: a later lookup must miss, not read it)
-    void erase(const Key128 &key) {
-        auto it = map.find(key);
-        if (it == map.end()) return;
-        const uint32_t s = it->second;
-        map.erase(it);
-        slots[s].used = false; slots[s].pending = false; slots[s].tick = 0;
-        free_slots.push_back(s);
-    }
-    void built(const Key128 &key) {
-        auto it = map.find(key);
-        if (it != map.end()) slots[it->second].pending = false;
-    }
-    std::vector<uint32_t> free_slots;
     void clear() {
         for (void *b : blocks) (void)hipFree(b);
-        blocks.clear(); slots.clear(); map.clear(); free_slots.clear();
+        blocks.clear();
+        ix.clear();
         if (ident) (void)hipFree(ident);
         ident = nullptr;
     }
 } g_tabs;
 
-// Tables lsa_g2_tables_prefetch has promised (their slots are taken, their keys resolve) but not yet built: built
-// when a Miller call arrives or when `batch()` of them are waiting, whichever is first -- always before anything on
-// lsa_stream() can read them.  One wavefront of k_g2_precomp holds five points and takes as long (0.65 ms) for five as
-// for one; further wavefronts run beside it.  A verifier that derives twenty G2 points one after the other
-// (CPPoly::verify, src/gadgets/poly.h:115-118) spends 0.45 ms of host time on them since the fixed-base tables of round 5,
-// so ONE launch of four workgroups when its Miller call arrives (0.65 ms) beats four launches of one queued behind each
-// other (2.6 ms: the round-4 setting, LSA_G2_PREFETCH_BATCH=5, which paid when a product took 0.27 ms of host time).
+// Tables lsa_g2_tables_prefetch has promised (g_tabs.ix.promised: their slots are taken, their keys resolve) but not yet
+// built: built when a Miller call arrives or when `batch()` of them are waiting, whichever is first (ix.flush_due) --
+// always before anything on lsa_stream() can read them.  One wavefront of k_g2_precomp holds five points and takes as
+// long (0.65 ms) for five as for one; further wavefronts run beside it.  A verifier that derives twenty G2 points one
+// after the other (CPPoly::verify, src/gadgets/poly.h:115-118) spends 0.45 ms of host time on them since the fixed-base
+// tables of round 5, so ONE launch of four workgroups when its Miller call arrives (0.65 ms) beats four launches of one
+// queued behind each other (2.6 ms: the round-4 setting, LSA_G2_PREFETCH_BATCH=5, which paid when a product took
+// 0.27 ms of host time).
 struct PendingTables {
-    std::vector<Jac<Fq2>> pts;
-    std::vector<uint64_t> dst;
-    std::vector<Key128> keys;
+    std::vector<Jac<Fq2>> pts;             // the points of g_tabs.ix.promised, in its order
     StageBuf dev;
     static size_t batch() {
-        static const size_t b = [] {
-            const char *e = getenv("LSA_G2_PREFETCH_BATCH");
-            const long v = e ? atol(e) : 60;
-            return (size_t)(v < 1 ? 1 : v > 1024 ? 1024 : v);
-        }();
+        static const size_t b = G2TableIndex::clamp_batch(getenv("LSA_G2_PREFETCH_BATCH") ? atol(getenv("LSA_G2_PREFETCH_BATCH")) : 60);
         return b;
     }
     int build(const std::vector<char> &h, size_t m) {
@@ -199,17 +157,16 @@ struct PendingTables {
         if (m == 0) return LSA_OK;
         std::vector<char> h(m * (sizeof(Jac<Fq2>) + 8));
         memcpy(h.data(), pts.data(), m * sizeof(Jac<Fq2>));
-        memcpy(h.data() + m * sizeof(Jac<Fq2>), dst.data(), m * 8);
-        const std::vector<Key128> ks = keys;
+        for (size_t k = 0; k < m; k++) {
+            const uint64_t dst = (uint64_t)(uintptr_t)g_tabs.ptr(g_tabs.ix.promised[k].slot);
+            memcpy(h.data() + m * sizeof(Jac<Fq2>) + k * 8, &dst, 8);
+        }
         pts.clear();
-        dst.clear();
-        keys.clear();
         const int rc = build(h, m);
-        // a promise that could not be kept is withdrawn: its key must miss from now on, not resolve to an unwritten table
-        for (const Key128 &k : ks) { if (rc) g_tabs.erase(k); else g_tabs.built(k); }
+        g_tabs.ix.settle_promises(rc == LSA_OK);
         return rc;
     }
-    void drop() { pts.clear(); dst.clear(); keys.clear(); }
+    void drop() { pts.clear(); g_tabs.ix.promised.clear(); }
 } g_pending;
 
 // ---------------------------------------------------------------- one job description
@@ -231,233 +188,154 @@ inline int force_kernel() {
     return f;
 }
 
+PairingShape shape_of(const Terms &t) {
+    PairingShape s;
+    s.n = t.n; s.seg = t.seg; s.nseg = t.nseg;
+    s.flags = t.flags != nullptr; s.blobs = t.qpre != nullptr; s.on_device = t.on_device;
+    s.force_m = g_force_m; s.force_kernel = force_kernel();
+    s.capacity = g_tabs.ix.capacity; s.max_pairs = miller_tab_max_pairs();
+    return s;
+}
+
+// ---------------------------------------------------------------- the pieces every route shares
+// the points of a host job on the device (d_q null: the route does not read the G2 points as a whole)
+int points_on_device(const Terms &t, const void **d_p, const void **d_q) {
+    *d_p = t.g1;
+    if (d_q) *d_q = t.g2;
+    if (t.on_device) return LSA_OK;
+    const size_t room = std::max<size_t>(t.n, 1);
+    if (g_pair_p.ensure(room * sizeof(Jac<Fq>)) || (d_q && g_pair_q.ensure(room * sizeof(Jac<Fq2>)))) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
+    if (t.n) {
+        LSA_UPLOAD(g_pair_p.p, t.g1, t.n * sizeof(Jac<Fq>));
+        if (d_q) LSA_UPLOAD(g_pair_q.p, t.g2, t.n * sizeof(Jac<Fq2>));
+    }
+    *d_p = g_pair_p.p;
+    if (d_q) *d_q = g_pair_q.p;
+    return LSA_OK;
+}
+
+// values -> products: g_pair_f holds nval values, product j is the product of the values [d_off[j], d_off[j+1]);
+// one_each: the values ARE the products.  (d_off is not read for a single product.)
+int products(size_t nval, bool one_each, const uint64_t *d_off, size_t nprod, void **d_res) {
+    if (one_each) { *d_res = g_pair_f.p; return LSA_OK; }
+    if (g_pair_s.ensure((nprod == 1 ? (nval + 7) / 8 + 1 : nprod) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
+    if (nprod == 1 && nval) return fq12_product_device(g_pair_f.p, g_pair_s.p, nval, d_res, g.stream);
+    *d_res = g_pair_s.p;
+    if (nprod == 1) {                      // the empty product
+        Fq12 one = Fq12::one();
+        HIPCHK(hipMemcpyAsync(g_pair_s.p, &one, sizeof one, hipMemcpyHostToDevice, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+        return LSA_OK;
+    }
+    return fq12_segment_products_device(g_pair_f.p, d_off, nprod, g_pair_s.p, g.stream);
+}
+
+// one Fq12 to the caller through the pinned mirror g.h_result (d_val null: a kernel has written it there already)
+int one_to_host(const void *d_val, void *out) {
+    if (d_val) HIPCHK(hipMemcpyAsync(g.h_result, d_val, fq12_bytes(), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    memcpy(out, g.h_result, fq12_bytes());
+    return LSA_OK;
+}
+
+// ---------------------------------------------------------------- the routes
 // The job through the fused kernel (pairing.hip, k_miller_fused: G2 arithmetic and Fq12 chain side by side in one
-// workgroup, one Miller value per term), then the products.  emit: per term, the device table to fill on the way
-// (0: none) -- the tables of points seen for the first time go into the cache while their first loop runs.
-int run_fused(const Terms &t, const std::vector<uint64_t> &emit, void **d_res) {
-    const size_t n = t.n, nprod = t.seg ? t.nseg : n;
-    int rc = wait_uploads();
+// workgroup, one Miller value per term), then the products.  fill_tables: the caller has resolved the job and left, per
+// term, the device table to fill on the way (0: none) at pl.off_tab of the pinned block -- the tables of points seen
+// for the first time go into the cache while their first loop runs.
+int run_fused(const Terms &t, const PairingShape &sh, const PairingPlan &pl, bool fill_tables, void **d_res) {
+    int rc = g_pin.wait();
     if (rc) return rc;
-    const size_t off_seg = 0, off_emit = off_seg + (nprod + 1) * 8, off_flag = off_emit + n * 8, meta_bytes = off_flag + n + 8;
-    if (g_pin_meta.ensure(meta_bytes) || g_pair_meta.ensure(meta_bytes) || g_pair_f.ensure(std::max<size_t>(n, 1) * fq12_bytes()) ||
-        g_pair_s.ensure(((n + 7) / 8 + nprod + 1) * fq12_bytes())) {
+    if (g_pin.meta.ensure(pl.meta_bytes) || g_pair_meta.ensure(pl.meta_bytes) || g_pair_f.ensure(std::max<size_t>(t.n, 1) * fq12_bytes())) {
         set_error("pairing: staging allocation failed");
         return LSA_ERR_NOMEM;
     }
-    char *hm = (char *)g_pin_meta.p;
-    uint64_t *h_seg = (uint64_t *)(hm + off_seg), *h_emit = (uint64_t *)(hm + off_emit);
-    uint8_t *h_flag = (uint8_t *)(hm + off_flag);
-    for (size_t j = 0; j <= nprod; j++) h_seg[j] = t.seg ? t.seg[j] : j;
-    for (size_t i = 0; i < n; i++) { h_emit[i] = emit.empty() ? 0 : emit[i]; h_flag[i] = t.flags ? (uint8_t)(t.flags[i] & 1) : (uint8_t)0; }
-    const void *d_p = t.g1, *d_q = t.g2;
-    if (!t.on_device) {
-        if (g_pair_p.ensure(std::max<size_t>(n, 1) * sizeof(Jac<Fq>)) || g_pair_q.ensure(std::max<size_t>(n, 1) * sizeof(Jac<Fq2>))) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        if (n) {
-            LSA_UPLOAD(g_pair_p.p, t.g1, n * sizeof(Jac<Fq>));
-            LSA_UPLOAD(g_pair_q.p, t.g2, n * sizeof(Jac<Fq2>));
-        }
-        d_p = g_pair_p.p; d_q = g_pair_q.p;
-    }
-    HIPCHK(hipMemcpyAsync(g_pair_meta.p, hm, meta_bytes, hipMemcpyHostToDevice, g.stream));
-    rc = mark_uploads();
+    pl.fill(sh, t.flags, (char *)g_pin.meta.p);
+    const void *d_p, *d_q;
+    rc = points_on_device(t, &d_p, &d_q);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(g_pair_meta.p, g_pin.meta.p, pl.meta_bytes, hipMemcpyHostToDevice, g.stream));
+    rc = g_pin.mark();
     if (rc) return rc;
     const char *dm = (const char *)g_pair_meta.p;
-    rc = miller_fused_device(d_p, d_q, (const uint8_t *)(dm + off_flag), emit.empty() ? nullptr : (uint32_t *const *)(dm + off_emit), n, g_pair_f.p, g.stream, t.gt_only);
+    rc = miller_fused_device(d_p, d_q, (const uint8_t *)(dm + pl.off_flag), fill_tables ? (uint32_t *const *)(dm + pl.off_tab) : nullptr, t.n, g_pair_f.p, g.stream, t.gt_only);
     if (rc) return rc;
-    if (!t.seg) { *d_res = g_pair_f.p; return LSA_OK; }
-    if (nprod == 1 && n > 0) return fq12_product_device(g_pair_f.p, g_pair_s.p, n, d_res, g.stream);
-    rc = fq12_segment_products_device(g_pair_f.p, (const uint64_t *)(dm + off_seg), nprod, g_pair_s.p, g.stream);
-    *d_res = g_pair_s.p;
-    return rc;
+    return products(t.n, !t.seg, (const uint64_t *)(dm + pl.off_prod), pl.nprod, d_res);
 }
 
-// Miller products of the job on the device: *d_res points at nseg Fq12 values when this returns (stream-ordered)
-int run_miller(const Terms &t, void **d_res) {
-    const size_t n = t.n, nseg = t.nseg;
-    g_tabs.read_env();
-    // ---- points the cache does not take (more than 1024 terms, device-resident, cache off): the fused kernel -- G2
-    // arithmetic and Fq12 chain side by side, no table through memory.  (LSA_MILLER_KERNEL = 6 forces it, 5 the tables.)
-    const bool no_cache = t.on_device || t.n > 1024 || g_tabs.max_tables == 0;
-    if (!t.qpre && t.n && g_force_m == 0 && ((force_kernel() == 0 && no_cache) || force_kernel() == 6)) return run_fused(t, {}, d_res);
-    // ---- the one-lane-per-pairing kernel of miller.h (the family's fallback): only when forced
-    const bool plain = !t.qpre && !t.flags;
-    if (plain && force_kernel() == 3) {
-        const void *d_p = t.g1, *d_q = t.g2;
-        if (!t.on_device) {
-            if (g_pair_p.ensure(n * sizeof(Jac<Fq>)) || g_pair_q.ensure(n * sizeof(Jac<Fq2>))) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-            LSA_UPLOAD(g_pair_p.p, t.g1, n * sizeof(Jac<Fq>));
-            LSA_UPLOAD(g_pair_q.p, t.g2, n * sizeof(Jac<Fq2>));
-            d_p = g_pair_p.p; d_q = g_pair_q.p;
-        }
-        if (g_pair_f.ensure((n ? n : 1) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        int rc = miller_device(d_p, d_q, n, g_pair_f.p, g.stream);
-        if (rc) return rc;
-        if (!t.seg) { *d_res = g_pair_f.p; return LSA_OK; }
-        if (nseg == 1) {
-            if (g_pair_s.ensure(((n + 7) / 8 + 1) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-            if (n == 0) { Fq12 one = Fq12::one(); HIPCHK(hipMemcpyAsync(g_pair_s.p, &one, sizeof one, hipMemcpyHostToDevice, g.stream)); HIPCHK(hipStreamSynchronize(g.stream)); *d_res = g_pair_s.p; return LSA_OK; }
-            return fq12_product_device(g_pair_f.p, g_pair_s.p, n, d_res, g.stream);
-        }
-        if (g_pair_s.ensure(nseg * fq12_bytes()) || g_pair_meta.ensure((nseg + 1) * sizeof(uint64_t))) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        LSA_UPLOAD(g_pair_meta.p, t.seg, (nseg + 1) * sizeof(uint64_t));
+// the one-lane-per-pairing kernel of miller.h
+int run_one_lane(const Terms &t, void **d_res) {
+    const void *d_p, *d_q;
+    int rc = points_on_device(t, &d_p, &d_q);
+    if (rc) return rc;
+    if (g_pair_f.ensure(std::max<size_t>(t.n, 1) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
+    rc = miller_device(d_p, d_q, t.n, g_pair_f.p, g.stream);
+    if (rc) return rc;
+    if (t.seg && t.nseg > 1) {
+        if (g_pair_meta.ensure((t.nseg + 1) * sizeof(uint64_t))) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
+        LSA_UPLOAD(g_pair_meta.p, t.seg, (t.nseg + 1) * sizeof(uint64_t));
         HIPCHK(hipStreamSynchronize(g.stream));     // t.seg is pageable caller memory
-        rc = fq12_segment_products_device(g_pair_f.p, (const uint64_t *)g_pair_meta.p, nseg, g_pair_s.p, g.stream);
-        *d_res = g_pair_s.p;
-        return rc;
     }
+    return products(t.n, !t.seg, (const uint64_t *)g_pair_meta.p, t.nseg, d_res);
+}
 
-    // ---- tables
-    { int rcw = wait_uploads(); if (rcw) return rcw; }
-    { int rcp = g_pending.flush(); if (rcp) return rcp; }       // promised tables: on the stream before anything reads them
-    if (g_tabs.ensure_ident()) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    g_tabs.tick++;
-    const size_t TW = g2_table_words(), PUB = g2_precomp_public_bytes();
-    // accumulators: a product of len pairs takes ceil(len / M) of them; M grows once the chip is full
-    // (four accumulators per wavefront, 1024 SIMDs)
-    unsigned M = 1;
-    while (M < miller_tab_max_pairs() && n > (size_t)M * 8192) M++;
-    if (g_force_m) M = g_force_m;
-    std::vector<uint64_t> own_seg;
-    const uint64_t *seg = t.seg;
-    size_t nprod = nseg;
-    if (!seg) {
-        own_seg.resize(n + 1);
-        for (size_t i = 0; i <= n; i++) own_seg[i] = i;
-        seg = own_seg.data();
-        nprod = n;
-    }
-    size_t nacc = 0;
-    for (size_t j = 0; j < nprod; j++) { const size_t len = (size_t)(seg[j + 1] - seg[j]); nacc += len ? (len + M - 1) / M : 1; }
-    // layout of the index arrays (one pinned staging buffer, one copy): table pointers, accumulator offsets,
-    // product offsets (in accumulators), flags
-    // (a handful of host G1 points ride in the same pinned buffer: one copy command for the whole call)
-    const bool g1_in_meta = !t.on_device && n > 0 && n <= 256;
-    const size_t off_tab = 0, off_acc = off_tab + n * 8, off_prod = (off_acc + (nacc + 1) * 4 + 7) & ~(size_t)7, off_flag = off_prod + (nprod + 1) * 8,
-                 off_g1 = (off_flag + n + 15) & ~(size_t)15, meta_bytes = off_g1 + (g1_in_meta ? n * sizeof(Jac<Fq>) : 0) + 8;
-    if (g_pin_meta.ensure(meta_bytes) || g_pair_meta.ensure(meta_bytes)) { set_error("pairing: staging allocation failed"); return LSA_ERR_NOMEM; }
-    char *hm = (char *)g_pin_meta.p;
-    uint64_t *h_tab = (uint64_t *)(hm + off_tab);
-    uint32_t *h_acc = (uint32_t *)(hm + off_acc);
-    uint64_t *h_prod = (uint64_t *)(hm + off_prod);
-    uint8_t *h_flag = (uint8_t *)(hm + off_flag);
-    {
-        size_t a = 0;
-        for (size_t j = 0; j < nprod; j++) {
-            h_prod[j] = a;
-            const size_t lo = (size_t)seg[j], hi = (size_t)seg[j + 1];
-            if (lo == hi) { h_acc[a++] = (uint32_t)lo; continue; }       // an empty product: one accumulator without pairs = 1
-            for (size_t s = lo; s < hi; s += M) h_acc[a++] = (uint32_t)s;
-        }
-        h_prod[nprod] = a;
-        h_acc[a] = (uint32_t)n;
-    }
-    // accumulator a covers [h_acc[a], min(h_acc[a+1], end of its product)): make that literally h_acc[a+1] by
-    // construction -- the next accumulator starts where this one ends, except after an empty product
-    // (same start) -- so nothing else is needed.
-    for (size_t i = 0; i < n; i++) h_flag[i] = t.flags ? (uint8_t)(t.flags[i] & 1) : (uint8_t)0;
-
-    // ---- resolve a device table for every term
-    const bool use_cache = !t.on_device && g_tabs.max_tables > 0 && n <= 1024;
-    std::vector<uint32_t> need_pre;        // terms whose table has to be computed from the point
-    std::vector<uint32_t> need_imp;        // terms whose table has to be imported from a precomp blob
-    size_t scratch_used = 0;
-    std::unordered_map<Key128, uint64_t, Key128Hash> seen;   // within this call
-    std::unordered_map<const void *, uint64_t> seen_blob;   // cache bypassed: equal blob POINTERS still share one table
-    auto scratch_slot = [&](size_t k) { return (uint64_t)(uintptr_t)((uint32_t *)g_pair_scratch_tabs.p + k * TW); };
+// Tables, stage 2: a device table for every term into h_tab; the terms whose table has to be computed from the point
+// (need_pre) or imported from a precomp blob (need_imp).  The only code that talks to the index during a call.
+int resolve_tables(const Terms &t, const PairingPlan &pl, uint64_t *h_tab, std::vector<uint32_t> &need_pre, std::vector<uint32_t> &need_imp) {
+    const size_t n = t.n, TW = g2_table_words(), PUB = g2_precomp_public_bytes();
     // every term is validated BEFORE the cache is touched: a call that fails half-way must not leave keys behind
     for (size_t i = 0; i < n; i++)
         if (!(t.qpre && t.qpre[i]) && !t.g2) { set_error("pairing: term %zu has neither a point nor a precomputed table", i); return LSA_ERR_INVALID; }
-    // uncached terms take scratch tables: count them first (the scratch buffer must not move afterwards).  With the
-    // cache: at worst all n (the cache full of this call's own tables, n <= 1024); without: one per point term and one
-    // per DISTINCT blob (verifyLin3or4 scaled up: 2^16 terms over a handful of key blobs are a handful of tables)
-    size_t scratch_need = n;
-    if (!use_cache && t.qpre) {
-        std::unordered_map<const void *, uint64_t> distinct;
+    // Equal keys within the call share one table.  With the cache the key is the fingerprint; without it blobs are
+    // keyed by their POINTER (verifyLin3or4 scaled up: 2^16 terms over a handful of key blobs are a handful of tables)
+    // and points are not compared at all.
+    std::unordered_map<Key128, uint64_t, Key128Hash> seen;
+    auto key_of = [&](size_t i, const void *blob) {
+        if (!pl.use_cache) return Key128{(uint64_t)(uintptr_t)blob, 0};
+        return blob ? g2_fingerprint(blob, PUB, 2) : g2_fingerprint((const char *)t.g2 + i * sizeof(Jac<Fq2>), sizeof(Jac<Fq2>), 1);
+    };
+    // uncached terms take scratch tables: sized first (the scratch buffer must not move afterwards).  With the cache: at
+    // worst all n (the cache full of this call's own tables, n <= 1024); without: one per point term and one per
+    // distinct blob, entered into `seen` without a table yet
+    size_t scratch_need = pl.scratch_max, scratch_used = 0;
+    if (!pl.use_cache && t.qpre) {
         scratch_need = 0;
-        for (size_t i = 0; i < n; i++) {
-            if (!t.qpre[i]) scratch_need++;
-            else if (distinct.emplace(t.qpre[i], 0).second) scratch_need++;
-        }
+        for (size_t i = 0; i < n; i++)
+            if (!t.qpre[i] || seen.emplace(key_of(i, t.qpre[i]), 0).second) scratch_need++;
     }
     if (g_pair_scratch_tabs.ensure(std::max<size_t>(scratch_need, 1) * TW * 4)) { set_error("pairing: table scratch allocation failed"); return LSA_ERR_NOMEM; }
-    // keys this call inserts: withdrawn again on ANY error return below (their tables would be unwritten or partial, and
-    // the next call with the same Q would run its Miller loop over them)
-    struct InsertGuard {
-        std::vector<Key128> keys;
-        bool ok = false;
-        ~InsertGuard() { if (!ok) for (const Key128 &k : keys) g_tabs.erase(k); }
-    } guard;
     for (size_t i = 0; i < n; i++) {
         const void *blob = t.qpre ? t.qpre[i] : nullptr;
-        uint64_t dev = 0;
-        if (use_cache) {
-            const Key128 key = blob ? fingerprint(blob, PUB, 2) : fingerprint((const char *)t.g2 + i * sizeof(Jac<Fq2>), sizeof(Jac<Fq2>), 1);
+        const bool shared = pl.use_cache || blob;
+        const Key128 key = key_of(i, blob);
+        if (shared) {
             auto it = seen.find(key);
-            if (it != seen.end()) dev = it->second;
-            else {
-                long s = g_tabs.lookup(key);
-                if (s >= 0) dev = (uint64_t)(uintptr_t)g_tabs.ptr((uint32_t)s);
-                else {
-                    s = g_tabs.insert(key);
-                    if (s >= 0) guard.keys.push_back(key);
-                    dev = s >= 0 ? (uint64_t)(uintptr_t)g_tabs.ptr((uint32_t)s) : scratch_slot(scratch_used++);
-                    (blob ? need_imp : need_pre).push_back((uint32_t)i);
-                }
-                seen.emplace(key, dev);
-            }
-        } else if (blob) {
-            auto it = seen_blob.find(blob);
-            if (it != seen_blob.end()) dev = it->second;
-            else {
-                dev = scratch_slot(scratch_used++);
-                seen_blob.emplace(blob, dev);
-                need_imp.push_back((uint32_t)i);
-            }
-        } else {
-            dev = scratch_slot(scratch_used++);
-            need_pre.push_back((uint32_t)i);
+            if (it != seen.end() && it->second) { h_tab[i] = it->second; continue; }
         }
-        h_tab[i] = dev;
+        long s = pl.use_cache ? g_tabs.ix.lookup(key) : -1;
+        if (s < 0) {
+            if (pl.use_cache) s = g_tabs.insert(key);
+            (blob ? need_imp : need_pre).push_back((uint32_t)i);
+        }
+        h_tab[i] = (uint64_t)(uintptr_t)(s >= 0 ? g_tabs.ptr((uint32_t)s) : (uint32_t *)g_pair_scratch_tabs.p + scratch_used++ * TW);
+        if (shared) seen[key] = h_tab[i];
     }
+    return LSA_OK;
+}
 
-    // ---- points seen for the first time and no precomputed tables among the terms: the fused kernel computes every
-    // term (while the chip is not full a resident Q gains nothing from its table: the call waits for the new ones
-    // anyway) and fills the new tables on the way
-    if (use_cache && !t.qpre && !need_pre.empty() && g_force_m == 0 && force_kernel() != 5) {
-        std::vector<uint64_t> emit(n, 0);
-        for (uint32_t i : need_pre) emit[i] = h_tab[i];
-        const int rcf = run_fused(t, emit, d_res);
-        guard.ok = rcf == LSA_OK;
-        return rcf;
-    }
-
-    // ---- uploads
-    const void *d_g1 = t.g1;
-    if (g1_in_meta) {
-        memcpy(hm + off_g1, t.g1, n * sizeof(Jac<Fq>));
-        d_g1 = (const char *)g_pair_meta.p + off_g1;
-    } else if (!t.on_device) {
-        if (g_pair_p.ensure(std::max<size_t>(n, 1) * sizeof(Jac<Fq>))) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        if (n) LSA_UPLOAD(g_pair_p.p, t.g1, n * sizeof(Jac<Fq>));
-        d_g1 = g_pair_p.p;
-    }
-    HIPCHK(hipMemcpyAsync(g_pair_meta.p, hm, meta_bytes, hipMemcpyHostToDevice, g.stream));
-    const char *dm = (const char *)g_pair_meta.p;
-
-    // ---- missing tables
+// Tables, stage 5: the tables of need_pre computed from their points, those of need_imp imported from their blobs
+int build_missing(const Terms &t, const PairingPlan &pl, const uint64_t *h_tab, const std::vector<uint32_t> &need_pre, const std::vector<uint32_t> &need_imp) {
+    const size_t PUB = g2_precomp_public_bytes();
     if (!need_pre.empty()) {
         const size_t m = need_pre.size();
-        const void *d_q = nullptr;
-        const uint32_t *const *d_tp = nullptr;
-        // the points and the destination pointers of the misses, gathered into pinned staging
-        if (g_pin_q.ensure(m * (sizeof(Jac<Fq2>) + 8)) || g_pair_q.ensure(m * (sizeof(Jac<Fq2>) + 8))) { set_error("pairing: staging allocation failed"); return LSA_ERR_NOMEM; }
-        char *hq = (char *)g_pin_q.p;
-        uint64_t *hp = (uint64_t *)(hq + m * sizeof(Jac<Fq2>));
-        if (t.on_device && m == n) {
-            d_q = t.g2;                                             // all of them, in place
-            d_tp = (const uint32_t *const *)(dm + off_tab);
-        } else {
-            if (t.on_device) { set_error("pairing: internal (device points need tables for all terms)"); return LSA_ERR_INVALID; }
+        const void *d_q = t.g2;                                                              // on the device: all of them, in place
+        const uint32_t *const *d_tp = (const uint32_t *const *)((const char *)g_pair_meta.p + pl.off_tab);
+        if (t.on_device && m != t.n) { set_error("pairing: internal (device points need tables for all terms)"); return LSA_ERR_INVALID; }
+        if (!t.on_device) {
+            // the points and the destination pointers of the misses, gathered into pinned staging
+            if (g_pin.q.ensure(m * (sizeof(Jac<Fq2>) + 8)) || g_pair_q.ensure(m * (sizeof(Jac<Fq2>) + 8))) { set_error("pairing: staging allocation failed"); return LSA_ERR_NOMEM; }
+            char *hq = (char *)g_pin.q.p;
+            uint64_t *hp = (uint64_t *)(hq + m * sizeof(Jac<Fq2>));
             for (size_t k = 0; k < m; k++) {
                 memcpy(hq + k * sizeof(Jac<Fq2>), (const char *)t.g2 + (size_t)need_pre[k] * sizeof(Jac<Fq2>), sizeof(Jac<Fq2>));
                 hp[k] = h_tab[need_pre[k]];
@@ -482,24 +360,64 @@ int run_miller(const Terms &t, void **d_res) {
         int rc = g2_table_import_device(g_pair_pub.p, m, (uint32_t *const *)((char *)g_pair_pub.p + m * PUB), g.stream);
         if (rc) return rc;
     }
+    return LSA_OK;
+}
 
-    { int rcm = mark_uploads(); if (rcm) return rcm; }
-    // ---- Miller loops, one Fq12 per accumulator
-    if (g_pair_f.ensure(std::max<size_t>(nacc, 1) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    int rc = miller_tab_device(d_g1, (const uint32_t *const *)(dm + off_tab), (const uint8_t *)(dm + off_flag), (const uint32_t *)(dm + off_acc), nacc, M,
-                               g_tabs.ident, g_pair_f.p, g.stream);
+// Miller products of the job on the device: *d_res points at nseg (or n) Fq12 values when this returns (stream-ordered)
+int run_miller(const Terms &t, void **d_res) {
+    const size_t n = t.n;
+    g_tabs.read_env();
+    // ---- 1. plan
+    const PairingShape sh = shape_of(t);
+    const PairingPlan pl = plan_pairing(sh);
+    if (pl.route == ROUTE_FUSED) return run_fused(t, sh, pl, false, d_res);
+    if (pl.route == ROUTE_ONE_LANE) return run_one_lane(t, d_res);
+    int rc = g_pin.wait();
     if (rc) return rc;
-    guard.ok = true;           // every new table is on the stream, ahead of anything that reads it
-    // ---- products over the accumulators of each product
-    if (nacc == nprod) { *d_res = g_pair_f.p; return LSA_OK; }
-    if (nprod == 1) {
-        if (g_pair_s.ensure(((nacc + 7) / 8 + 1) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-        return fq12_product_device(g_pair_f.p, g_pair_s.p, nacc, d_res, g.stream);
+    rc = g_pending.flush();                 // promised tables: on the stream before anything reads them
+    if (rc) return rc;
+    if (g_tabs.ensure_ident()) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
+    g_tabs.ix.tick++;
+    if (g_pin.meta.ensure(pl.meta_bytes) || g_pair_meta.ensure(pl.meta_bytes)) { set_error("pairing: staging allocation failed"); return LSA_ERR_NOMEM; }
+    char *hm = (char *)g_pin.meta.p;
+    const char *dm = (const char *)g_pair_meta.p;
+    uint64_t *h_tab = (uint64_t *)(hm + pl.off_tab);
+    pl.fill(sh, t.flags, hm);
+    // ---- 2. a device table for every term
+    G2TableIndex::CallGuard guard(g_tabs.ix);
+    std::vector<uint32_t> need_pre, need_imp;
+    rc = resolve_tables(t, pl, h_tab, need_pre, need_imp);
+    if (rc) return rc;
+    // ---- 3. points seen for the first time and no precomputed tables among the terms: the fused kernel computes every
+    // term (while the chip is not full a resident Q gains nothing from its table: the call waits for the new ones
+    // anyway) and fills the new tables on the way.  h_tab stays where it is (as_fused) and keeps the new tables only.
+    if (pl.may_fill && !need_pre.empty()) {
+        for (size_t i = 0, k = 0; i < n; i++) {
+            if (k < need_pre.size() && need_pre[k] == i) k++;
+            else h_tab[i] = 0;
+        }
+        rc = run_fused(t, sh, pl.as_fused(n), true, d_res);
+        if (rc == LSA_OK) guard.commit();
+        return rc;
     }
-    if (g_pair_s.ensure(nprod * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
-    rc = fq12_segment_products_device(g_pair_f.p, (const uint64_t *)(dm + off_prod), nprod, g_pair_s.p, g.stream);
-    *d_res = g_pair_s.p;
-    return rc;
+    // ---- 4. uploads: a handful of host G1 points ride in the index block (one copy command for the whole call)
+    const void *d_g1 = dm + pl.off_g1;
+    if (pl.g1_in_meta) memcpy(hm + pl.off_g1, t.g1, n * sizeof(Jac<Fq>));
+    else if ((rc = points_on_device(t, &d_g1, nullptr))) return rc;
+    HIPCHK(hipMemcpyAsync(g_pair_meta.p, hm, pl.meta_bytes, hipMemcpyHostToDevice, g.stream));
+    // ---- 5. missing tables
+    rc = build_missing(t, pl, h_tab, need_pre, need_imp);
+    if (rc) return rc;
+    rc = g_pin.mark();
+    if (rc) return rc;
+    // ---- 6. Miller loops, one Fq12 per accumulator
+    if (g_pair_f.ensure(std::max<size_t>(pl.nacc, 1) * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
+    rc = miller_tab_device(d_g1, (const uint32_t *const *)(dm + pl.off_tab), (const uint8_t *)(dm + pl.off_flag), (const uint32_t *)(dm + pl.off_acc), pl.nacc, pl.M,
+                           g_tabs.ident, g_pair_f.p, g.stream);
+    if (rc) return rc;
+    guard.commit();            // every new table is on the stream, ahead of anything that reads it
+    // ---- 7. products over the accumulators of each product
+    return products(pl.nacc, pl.nacc == pl.nprod, (const uint64_t *)(dm + pl.off_prod), pl.nprod, d_res);
 }
 
 // the job with host results: out = nseg (or n) Fq12 values
@@ -519,10 +437,7 @@ int run_terms_host(const Terms &t_in, void *out, bool final_exp) {
         // one check = one value: the final exponentiation writes it straight into pinned host memory (no copy command
         // behind the kernel: ~15 us of every blocking check of a verifier written call by call)
         rc = final_exp_device(res, 1, g.h_result, g.stream);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(g.stream));
-        memcpy(out, g.h_result, fq12_bytes());
-        return LSA_OK;
+        return rc ? rc : one_to_host(nullptr, out);
     }
     if (final_exp) {
         if (g_pair_o.ensure(nres * fq12_bytes())) { set_error("pairing: hipMalloc failed"); return LSA_ERR_NOMEM; }
@@ -547,9 +462,7 @@ int check_segments(const uint64_t *seg, size_t nseg, const char *who) {
 
 namespace lsa {
 void pairing_release() {
-    g_pin_meta.release(); g_pin_q.release();           // (the StageBufs above: stage_release_all, staging.h)
-    if (g_uploaded) { (void)hipEventDestroy(g_uploaded); g_uploaded = nullptr; }
-    g_upload_pending = false;
+    g_pin.release();                                   // (the StageBufs above: stage_release_all, staging.h)
     g_pending.drop();
     miller_split_release();
     g_tabs.clear();
@@ -567,14 +480,14 @@ int lsa_g2_precompute(const void *g2_jac, size_t n, void *out_precomp) {
     if (n == 0) return LSA_OK;
     if (!g2_jac || !out_precomp) { set_error("g2_precompute: null argument"); return LSA_ERR_INVALID; }
     const size_t TW = g2_table_words(), PUB = g2_precomp_public_bytes();
-    if (g_pair_q.ensure(n * sizeof(Jac<Fq2>)) || g_pair_scratch_tabs.ensure(n * TW * 4) || g_pair_pub.ensure(n * PUB) || g_pin_meta.ensure(n * 8) ||
+    if (g_pair_q.ensure(n * sizeof(Jac<Fq2>)) || g_pair_scratch_tabs.ensure(n * TW * 4) || g_pair_pub.ensure(n * PUB) || g_pin.meta.ensure(n * 8) ||
         g_pair_meta.ensure(n * 8)) {
         set_error("g2_precompute: staging allocation failed");
         return LSA_ERR_NOMEM;
     }
-    rc = wait_uploads();
+    rc = g_pin.wait();
     if (rc) return rc;
-    uint64_t *hp = (uint64_t *)g_pin_meta.p;
+    uint64_t *hp = (uint64_t *)g_pin.meta.p;
     for (size_t i = 0; i < n; i++) hp[i] = (uint64_t)(uintptr_t)((uint32_t *)g_pair_scratch_tabs.p + i * TW);
     HIPCHK(hipMemcpyAsync(g_pair_meta.p, hp, n * 8, hipMemcpyHostToDevice, g.stream));
     LSA_UPLOAD(g_pair_q.p, g2_jac, n * sizeof(Jac<Fq2>));
@@ -597,23 +510,21 @@ int lsa_g2_tables_prefetch(const void *g2_jac, size_t n) {
     if (n == 0) return LSA_OK;
     if (!g2_jac) { set_error("g2_tables_prefetch: null argument"); return LSA_ERR_INVALID; }
     g_tabs.read_env();
-    if (g_tabs.max_tables == 0 || n > 1024) return LSA_OK;         // nothing to keep them in
-    g_tabs.tick++;
+    G2TableIndex &ix = g_tabs.ix;
+    if (ix.capacity == 0 || n > PAIRING_CACHE_MAX_TERMS) return LSA_OK;         // nothing to keep them in
+    ix.tick++;
     for (size_t i = 0; i < n; i++) {
         const char *q = (const char *)g2_jac + i * sizeof(Jac<Fq2>);
-        const Key128 key = fingerprint(q, sizeof(Jac<Fq2>), 1);
-        if (g_tabs.lookup(key) >= 0) continue;
+        const Key128 key = g2_fingerprint(q, sizeof(Jac<Fq2>), 1);
+        if (ix.lookup(key) >= 0) continue;
         const long s = g_tabs.insert(key, true);                    // pending: no later insert may evict it before it is built
         if (s < 0) continue;                                        // full of tables of this very call: leave it to the Miller call
         Jac<Fq2> pt;
         memcpy(&pt, q, sizeof pt);
         g_pending.pts.push_back(pt);
-        g_pending.dst.push_back((uint64_t)(uintptr_t)g_tabs.ptr((uint32_t)s));
-        g_pending.keys.push_back(key);
+        ix.promise(key, (uint32_t)s);
     }
-    // (a cache smaller than a batch could hand a promised slot to somebody else before it is built)
-    if (g_pending.pts.size() >= PendingTables::batch() || g_tabs.max_tables < 4 * PendingTables::batch()) return g_pending.flush();
-    return LSA_OK;
+    return ix.flush_due(PendingTables::batch()) ? g_pending.flush() : LSA_OK;
 }
 
 int lsa_pairing_set_chunk(unsigned pairs_per_accumulator) {
@@ -628,12 +539,13 @@ int lsa_g2_table_cache(size_t max_tables) {
     HIPCHK(hipStreamSynchronize(g.stream));
     g_tabs.env_read = true;
     g_tabs.clear();
-    g_tabs.max_tables = max_tables;
+    g_tabs.ix.set_capacity(max_tables);
     return LSA_OK;
 }
 int lsa_g2_table_cache_stats(uint64_t out[4]) {
     if (!out) return LSA_ERR_INVALID;
-    out[0] = g_tabs.hits; out[1] = g_tabs.misses; out[2] = g_tabs.slots.size(); out[3] = g_tabs.evictions;
+    const G2TableIndex &ix = g_tabs.ix;
+    out[0] = ix.hits; out[1] = ix.misses; out[2] = ix.slots.size(); out[3] = ix.evictions;
     return LSA_OK;
 }
 
@@ -708,10 +620,7 @@ static int product_host(const void *g1, const void *g2, size_t n, void *out, boo
         if (rc) return rc;
         res = g_pair_o.p;
     }
-    HIPCHK(hipMemcpyAsync(g.h_result, res, fq12_bytes(), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    memcpy(out, g.h_result, fq12_bytes());
-    return LSA_OK;
+    return one_to_host(res, out);
 }
 int lsa_miller_loop_product(const void *g1, const void *g2, size_t n, void *out) { return product_host(g1, g2, n, out, false, false); }
 int lsa_pairing_product(const void *g1, const void *g2, size_t n, void *out) { return product_host(g1, g2, n, out, true, false); }
@@ -747,11 +656,7 @@ int lsa_fq12_product(const void *in, size_t n, void *out) {
     if (g_pair_f.ensure(n * fq12_bytes()) || g_pair_s.ensure(((n + 7) / 8 + 1) * fq12_bytes())) { set_error("fq12_product: hipMalloc failed"); return LSA_ERR_NOMEM; }
     LSA_UPLOAD(g_pair_f.p, in, n * fq12_bytes());
     rc = fq12_product_device(g_pair_f.p, g_pair_s.p, n, &res, g.stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g.h_result, res, fq12_bytes(), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    memcpy(out, g.h_result, fq12_bytes());
-    return LSA_OK;
+    return rc ? rc : one_to_host(res, out);
 }
 int lsa_final_exponentiation(const void *in, size_t n, void *out, int on_device) {
     LSA_TRACE_CALL("final_exponentiation", n);

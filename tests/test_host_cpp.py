@@ -9,7 +9,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name", ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges", "test_crs_index"])
+@pytest.mark.parametrize("name", ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges", "test_crs_index", "test_g2_table_index", "test_pairing_plan"])
 def test_host_cpp(name, tmp_path):
     src = os.path.join(ROOT, "tests", "cpp", name + ".cc")
     if not os.path.exists(src):
@@ -66,7 +66,7 @@ def test_host_64_bit_limbs_agree_with_the_device_limbs(tmp_path):
 # an out-of-range index into a limb array) is undefined in the kernels too, where nothing reports it.  Pure host code
 # only: the two programs that link the HIP library (test_shim_io.cc, test_shim_domains.cc) stay out of this tier.
 SANITIZE = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges", "test_crs_index"]
+_HEADER_TESTS = ["test_fp29", "test_glv", "test_fp29x2", "test_tower29", "test_smul", "test_w12", "test_tmiller", "test_inv29", "test_ntt_core", "test_msm_plan", "test_w12_edges", "test_crs_index", "test_g2_table_index", "test_pairing_plan"]
 _COLS = ["-DLSA_FP29_COLS", "-DLSA_F29_COLS", "-DLSA_FR29_COLS"]
 SANITIZED_PROGRAMS = ([(n, n, []) for n in _HEADER_TESTS]
                       + [(n + "_cols", n, _COLS) for n in ["test_fp29", "test_fp29x2", "test_tmiller", "test_w12", "test_ntt_core", "test_w12_edges"]]
